@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: LPCNet synthesis samples/s on synthetic 3-second utterances.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1          # the headline figure only
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full   # + every other leg described below
+    python bench.py ... --dump-outputs DIR                  # + DIR/pcm.npy: the PCM of the last timed step
     python bench.py --gpus 8 ...          # starts one rank per GPU itself (torch.distributed.run child)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,7 +13,9 @@ over one batch of --streams independent 3 s utterances per GPU (BASELINE config 
 utterances on one MI355X; with N GPUs the global list of N x 256 utterances is split by
 `parallel.shard_range`: config 4, weak scaling, no collective in the data path - RCCL only
 gathers the report).  Inputs (features, seeds, weights) are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line.  Outside the timed region the line also carries BASELINE
+region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the line
+(`roofline` is arithmetic on the timed steps' own HIP-event times plus the committed counter records).  With
+--full, outside the timed region, the line also carries BASELINE
 config 5 (`e2e`: predictor + residual VQ encode -> ceps2lpc -> decode on this rank's share of
 128 x N utterances, codebook-usage histograms summed over all ranks before the entropy, as
 src/generate_qtz_features.py:184,202 sums them over utterances; `two_batches_one_decode` /
@@ -179,6 +183,28 @@ def counters_record(kernel, khash):
         if rec and rec.get("kernel_source_sha256") == khash:
             return dict(rec, source=f"profiles/{name}")
     return None
+
+
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: all files of all ranks together stay below this
+
+
+def dump_outputs(dirname, pcm, rank, world):
+    """--dump-outputs: what a caller of the timed path receives, the (B, T*160) PCM block of this rank's last timed step,
+    as float32 `pcm.npy` (`pcm_rank<r>.npy` with several ranks).  A block larger than this rank's share of DUMP_BYTES
+    is cut to a fixed, seeded choice of whole utterances (the same rows for the same arguments).  Returns what was written."""
+    a = pcm.cpu().numpy()
+    B, n = a.shape
+    budget = DUMP_BYTES // world - 4096  # (the .npy header)
+    rows = np.arange(B)
+    if B * n * 4 > budget:
+        keep = max(1, budget // (n * 4))
+        rows = np.sort(np.random.default_rng(20221104).choice(B, keep, replace=False))
+        n = min(n, budget // 4)  # (one utterance longer than the whole budget: its head)
+    os.makedirs(dirname, exist_ok=True)
+    name = "pcm" if world == 1 else f"pcm_rank{rank}"
+    np.save(os.path.join(dirname, name + ".npy"), a[rows, :n].astype(np.float32))
+    return {"file": name + ".npy", "shape": [int(rows.size), int(n)],
+            "utterances": "all" if rows.size == B and n == a.shape[1] else [int(r) for r in rows]}
 
 
 def _pci_bus_id(dev):
@@ -467,8 +493,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--streams", type=int, default=256, help="utterances per GPU per step")
     ap.add_argument("--secs", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip BASELINE config 5 (extra key 'e2e', outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (e2e, many_stream, single_stream, voiced_50, "
+                         "cpu_baseline); off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the PCM of the last timed step as float32 DIR/pcm.npy (64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip BASELINE config 5 (extra key 'e2e', outside the timed region)")
     ap.add_argument("--e2e", action="store_true", help="(default; kept for older command lines)")
     ap.add_argument("--dump-pcm", default=None, help="directory: every rank saves its PCM block and shard range (tests)")
     args = ap.parse_args()
@@ -559,6 +591,7 @@ def main():
     if args.dump_pcm:
         os.makedirs(args.dump_pcm, exist_ok=True)
         np.savez(os.path.join(args.dump_pcm, f"rank{rank}.npz"), pcm=pcm.cpu().numpy(), lo=lo, hi=hi)
+    dumped = dump_outputs(args.dump_outputs, pcm, rank, world) if args.dump_outputs else None  # (before --full reuses pcm)
 
     # HBM bytes per k_decode launch: PMC counters cannot be read inside this process, so the figure comes from the
     # committed PMC passes (tools/traffic_round.sh) -- but only from a record taken on THIS kernel (hash of the decode
@@ -605,10 +638,14 @@ def main():
             "occupancy": counters_record("k_decode", khash),
         },
     }
+    if dumped:
+        out["dumped_outputs"] = dumped  # (rank 0's file; every rank writes its own)
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         e2e = e2e_config5(voc, torch, synth, parallel, rank, world)  # every rank: holds the report's collectives
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(out), flush=True)
+    elif rank == 0:  # --full: every other leg, outside the timed region
         # single-stream latency view (BASELINE config 2), outside the timed region
         one = torch.empty(1, T * 160, dtype=torch.int16, device="cuda")
         voc.synthesize(feats[:1], seeds[:1], out=one)

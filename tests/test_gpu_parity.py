@@ -813,7 +813,7 @@ def test_bench_rank_path_two_ranks_one_gpu(torch_cuda, synth, tmp_path):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                         "--gpus", "2", "--steps", "1", "--warmup", "1", "--streams", "8", "--secs", "1",
-                        "--no-cpu-baseline", "--dump-pcm", dump],
+                        "--full", "--no-cpu-baseline", "--dump-pcm", dump],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -852,7 +852,8 @@ def test_bench_rccl_branch_single_rank(torch_cuda, tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                        "--gpus", "1", "--steps", "1", "--warmup", "1", "--streams", "8", "--secs", "1", "--no-cpu-baseline"],
+                        "--gpus", "1", "--steps", "1", "--warmup", "1", "--streams", "8", "--secs", "1", "--full",
+                        "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -861,6 +862,40 @@ def test_bench_rccl_branch_single_rank(torch_cuda, tmp_path):
     pr = j["e2e"]["predictor_roofline"]  # the predictor kernels against the f32 MFMA peak
     assert pr["bound"] == "mfma" and pr["kernel"] == "k_encode_wsd" and 0.0 < pr["frac"] < 1.0 and 0.0 < pr["forward_frac"] < 1.0
     assert abs(pr["achieved"] - pr["algorithmic_flop"] / (pr["kernel_ms"] * 1e-3) / 1e12) < 1e-6
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(torch_cuda, synth, tmp_path):
+    """a plain `bench.py` run carries the headline keys and none of the legs that moved behind --full, honours --steps, and
+    --dump-outputs writes the PCM of the timed path as float32 `pcm.npy`: equal to a direct decode of the same utterances"""
+    import json
+    import subprocess
+    import sys
+    torch = torch_cuda
+    from fpcodec_amd.ceps2lpc import ceps2lpc_v
+    from fpcodec_amd.lpcnet import LPCNet
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = str(tmp_path / "out")
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "FPC_BENCH_BACKEND", "FPC_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--streams", "8", "--secs", "1", "--dump-outputs", dump],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    S, T = 8, 100
+    assert j["steps"] == 2 and j["unit"] == "samples/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert abs(j["value"] * j["ms_per_step"] / 1e3 - S * (T * 160 - 17)) < 1.0  # samples of one step / seconds of one step
+    assert j["ranks"][0]["samples"] == 2 * S * (T * 160 - 17)                  # ... and two steps were timed
+    for k in ("e2e", "many_stream", "single_stream", "voiced_50", "cpu_baseline"):
+        assert k not in j, k
+    assert os.listdir(dump) == ["pcm.npy"] and j["dumped_outputs"]["utterances"] == "all"
+    got = np.load(os.path.join(dump, "pcm.npy"))
+    base = synth.vocoder_features_raw(S, T, utt0=0)
+    feats = torch.from_numpy(base).cuda()
+    feats[:, :, 20:] = ceps2lpc_v(feats.reshape(-1, 36)[:, :20].contiguous())[1].reshape(S, T, 16)
+    want = LPCNet(synth.lpcnet_weights()).synthesize(feats, synth.seeds(S)).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want.shape and np.array_equal(got, want.astype(np.float32))
 
 
 def test_train_cb_stage_loop_vs_reference_golden(torch_cuda, synth, golden, tmp_path):

@@ -15,7 +15,7 @@ for f in glob.glob(os.path.join(o, "prof", "**", "*kernel_trace.csv"), recursive
                          r.get("VGPR_Count", ""), r.get("LDS_Block_Size", "")))
 rows.sort()
 with open(os.path.join(P, "r05_kernel_trace_k_decode.txt"), "w") as f:
-    f.write(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline   (tree {head})\n")
+    f.write(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline   (tree {head})\n")
     f.write("k_decode launches in time order: duration ms, grid size, VGPRs, LDS bytes\n")
     for _, ms, g, v, l in rows:
         f.write(f"  {ms:9.3f}  grid {g}  vgpr {v}  lds {l}\n")

@@ -7,9 +7,9 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out/r04m; rm -rf $o; mkdir -p $o
 git rev-parse HEAD > $o/head.txt 2>/dev/null || true
 python3 -c "import sys; sys.path.insert(0,'.'); from fpcodec_amd import _lib; print(_lib.lib().fpc_build_info().decode())" > $o/build_info.txt
-echo "== bench (20 steps)"; timeout -k 10 500 python bench.py --steps 20 --warmup 2 > $o/bench.json 2> $o/bench.err; tail -c 300 $o/bench.json; echo
+echo "== bench (20 steps)"; timeout -k 10 500 python bench.py --steps 20 --warmup 2 --full > $o/bench.json 2> $o/bench.err; tail -c 300 $o/bench.json; echo
 echo "== rocprofv3 kernel stats of the bench command"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o runc -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $o/prof_bench.json 2> $o/prof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o runc -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $o/prof_bench.json 2> $o/prof.err
 echo "== HBM traffic passes (k_decode)"; TAG=r04 bash tools/traffic_round.sh > $o/traffic.log 2>&1; tail -2 $o/traffic.log
 echo "== SQ counters (k_decode)"; bash tools/pmc_decode.sh r04final > $o/pmc_decode.txt 2>&1; tail -20 $o/pmc_decode.txt
 echo "== phase stamps"; FPC_DECODE_STAMPS=1 timeout -k 10 300 python tools/stamp_probe.py 256 2>&1 | grep -v amdgpu.ids | tail -16 > $o/stamps.txt
