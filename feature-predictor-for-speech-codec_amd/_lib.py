@@ -21,6 +21,8 @@ SYMBOLS = [
     "fpc_lpcnet_last_streams_per_workgroup", "fpc_lpcnet_paired_utterances",
     "fpc_trainer_create", "fpc_trainer_destroy", "fpc_trainer_step", "fpc_trainer_export",
     "fpc_cb_workspace_bytes", "fpc_cb_find_nearest", "fpc_cb_update", "fpc_cb_mean0", "fpc_kmeans1d",
+    "fpc_entropy_models_create", "fpc_entropy_models_destroy", "fpc_bitstream_bound", "fpc_bitstream_pack",
+    "fpc_bitstream_unpack",
 ]
 
 
@@ -128,6 +130,16 @@ def lib():
                                             C.c_void_p, C.c_void_p, C.c_void_p]
         L.fpc_lpcnet_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        sizes5 = C.POINTER(C.c_int)
+        L.fpc_entropy_models_create.argtypes = [sizes5, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.fpc_entropy_models_destroy.argtypes = [C.c_void_p]
+        L.fpc_entropy_models_destroy.restype = None
+        L.fpc_bitstream_bound.restype = C.c_longlong
+        L.fpc_bitstream_bound.argtypes = [sizes5, C.c_int, C.c_int]
+        L.fpc_bitstream_pack.argtypes = [sizes5, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                         C.c_void_p, C.c_void_p]
+        L.fpc_bitstream_unpack.argtypes = [sizes5, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p]
         _lib = L
     return _lib
 

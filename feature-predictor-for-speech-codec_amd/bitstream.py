@@ -13,8 +13,15 @@ from the below-threshold one).  Frame layout, MSB first:
 which is the fixed-length counterpart of the entropy figure `generate_qtz_features.py:94-101,202` reports
 (entropy per used codebook x usage + 2 flag bits).  The pitch columns are side information and not part of
 this stream.  Pure host code (numpy); the GPU work is on either side of it (`fpc_encode`,
-`fpc_decode_features`)."""
+`fpc_decode_features`).
+
+`pack_batch` / `unpack_batch` at the end produce and read the same bytes for a whole batch on the device
+(csrc/bitstream.hip); the host functions are their specification."""
+import ctypes as C
+
 import numpy as np
+
+from . import _lib
 
 
 def _bits(n):
@@ -151,6 +158,31 @@ class Models:
         self.f1 = Model([1.0 - keep[0], keep[0]])
         self.f2 = Model([1.0 - keep[1], keep[1]])
 
+    _h = None  # fpc_entropy_models of the device coder, made on first use
+
+    def cum_array(self):
+        """every cumulative table as uint32, back to back in the order fpc_entropy_models_create reads them:
+        [f1 | f2 | scl_hi | scl_lo | v0 | v1 | vlo], absent books left out"""
+        tabs = (self.f1, self.f2, self.scl_hi, self.scl_lo, self.v0, self.v1, self.vlo)
+        return np.concatenate([m.cum for m in tabs if m is not None]).astype(np.uint32)
+
+    def device_handle(self):
+        if self._h is None:
+            _lib.require_gpu()
+            cum, h = self.cum_array(), C.c_void_p()
+            _lib.check(_lib.lib().fpc_entropy_models_create(_sizes_arg(self.lay), cum.ctypes.data, C.byref(h)),
+                       "fpc_entropy_models_create")
+            self._h = h
+        return self._h
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                _lib.lib().fpc_entropy_models_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
 
 def _fields(idx, lay):
     """yield (model name, symbol) in stream order for one utterance"""
@@ -258,3 +290,52 @@ def entropy_unpack(data, nframes, models):
         elif lay.N_lo:
             out[i, 3] = get("vlo")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Both framings for a whole batch on the device (fpc_bitstream_pack / fpc_bitstream_unpack, include/fpcodec.h):
+# the same bytes as pack / entropy_pack above, without the symbols leaving the GPU.  No CPU fallback.
+# ---------------------------------------------------------------------------------------------
+def _sizes_arg(sizes):
+    lay = sizes if isinstance(sizes, Layout) else Layout(sizes)
+    return (C.c_int * 5)(lay.n_hi, lay.n_lo, lay.N_hi0, lay.N_hi1, lay.N_lo)
+
+
+def bound(sizes, L, entropy=False):
+    """bytes per utterance of L frames that always suffice (fpc_bitstream_bound)"""
+    n = _lib.lib().fpc_bitstream_bound(_sizes_arg(sizes), int(bool(entropy)), int(L))
+    if n < 0:
+        _lib.check(n, "fpc_bitstream_bound")
+    return int(n)
+
+
+def pack_batch(idx, sizes, models=None):
+    """idx (B, L, 4): a tensor on the GPU, or a numpy array (copied there) -> (bytes uint8 (B, stride), nbits int32 (B,)),
+    both on the device; models = None: fixed-length framing, a `Models`: entropy-coded.  Row b holds ceil(nbits[b] / 8)
+    bytes and zeros after them; nbits[b] = -1 (and a zero row) if the symbols of utterance b contradict the layout."""
+    import torch
+    _lib.require_gpu()
+    idx = torch.as_tensor(idx).to("cuda", torch.int32).contiguous()
+    B, L, four = idx.shape
+    assert four == 4
+    stride = bound(sizes, L, models is not None)
+    data = torch.empty(B, stride, dtype=torch.uint8, device=idx.device)
+    nbits = torch.empty(B, dtype=torch.int32, device=idx.device)
+    _lib.check(_lib.lib().fpc_bitstream_pack(
+        _sizes_arg(sizes), models.device_handle() if models is not None else None, idx.data_ptr(), B, L, data.data_ptr(),
+        stride, nbits.data_ptr(), _lib.stream_ptr()), "fpc_bitstream_pack")
+    return data, nbits
+
+
+def unpack_batch(data, L, sizes, models=None):
+    """inverse of pack_batch: data (B, stride) uint8 (tensor or numpy array, rows zero padded) -> idx int32 (B, L, 4) on
+    the device in the encoder's convention"""
+    import torch
+    _lib.require_gpu()
+    data = torch.as_tensor(data).to("cuda", torch.uint8).contiguous()
+    B, stride = data.shape
+    idx = torch.empty(B, int(L), 4, dtype=torch.int32, device=data.device)
+    _lib.check(_lib.lib().fpc_bitstream_unpack(
+        _sizes_arg(sizes), models.device_handle() if models is not None else None, data.data_ptr(), stride, B, int(L),
+        idx.data_ptr(), _lib.stream_ptr()), "fpc_bitstream_unpack")
+    return idx

@@ -31,7 +31,9 @@ extern "C" {
  * 3: exports fpc_kmeans1d (scalar-codebook k-means) and fpc_predictor_fallback_groups; fpc_predictor_forward keeps a scratch
  *    block in the handle (relu(h2) of all frames for the batched output layer).
  * 4: exports fpc_lpcnet_set_pairing and fpc_lpcnet_last_streams_per_workgroup (fpc_lpcnet_synthesize decodes two utterances
- *    per workgroup when the batch exceeds the device's compute units), fpc_lpcnet_paired_utterances and fpc_selftest. */
+ *    per workgroup when the batch exceeds the device's compute units), fpc_lpcnet_paired_utterances and fpc_selftest.
+ *    Added within 4 (new exports only, nothing existing changed; a binding written against the earlier set keeps working):
+ *    fpc_entropy_models_create / _destroy, fpc_bitstream_bound, fpc_bitstream_pack, fpc_bitstream_unpack. */
 #define FPC_ABI_VERSION 4
 #define FPC_API __attribute__((visibility("default")))
 
@@ -218,6 +220,39 @@ FPC_API int fpc_encode(fpc_predictor* p, const fpc_codebooks* cb, const float* f
  * a symbol lies outside its codebook. */
 FPC_API int fpc_decode_features(fpc_predictor* p, const fpc_codebooks* cb, const float* pitch_dev,
                         const int32_t* idx_dev, int B, int L, float* c_out_dev, fpc_stream s);
+
+/* ---- the bitstream between fpc_encode and fpc_decode_features (no reference counterpart) ----
+ * Device-side pack / unpack of a whole batch of symbol arrays idx [B,L,4] (fpc_encode's convention) in the two framings of
+ * fpcodec_amd/bitstream.py, whose pure-Python functions stay the specification: the bytes are theirs, bit for bit.
+ *   fixed-length   (models = NULL): per frame, MSB first, 2 flag bits and the ceil(log2 size) wide indices of bitstream.Layout
+ *   entropy-coded  (models != NULL): the static Witten-Neal-Cleary arithmetic coder with a 32-bit range over the same fields
+ *                  (bitstream.entropy_pack), one cumulative-frequency table per field
+ * sizes = (n_hi, n_lo, N_hi0, N_hi1, N_lo), the codebook sizes (0 = book absent; each <= 65536, n_hi and N_hi0 >= 1): no
+ * codebook or predictor handle is needed.  Work split: csrc/bitstream.hip. */
+typedef struct fpc_entropy_models fpc_entropy_models;
+/* cum_host: the cumulative counts of every field as uint32, tables back to back in the order
+ * [f1 (3) | f2 (3) | scl_hi (n_hi + 1) | scl_lo | v0 | v1 | vlo]; an absent book contributes nothing.  (The float64 scaling
+ * of histograms into counts is bitstream.Model's: both sides use the same integers.)  Each table must start at 0, increase
+ * strictly and end at a total <= 65536, else FPC_ERR_INVALID; FPC_ERR_CAPACITY if the tables exceed 64 KiB of LDS. */
+FPC_API int fpc_entropy_models_create(const int sizes[5], const uint32_t* cum_host, fpc_entropy_models** out);
+FPC_API void fpc_entropy_models_destroy(fpc_entropy_models* m);
+/* Bytes per utterance of L frames that always suffice (a pure function, no device needed; < 0: a negative fpc_status).
+ * Fixed-length: the widest frame x L, exact.  Entropy-coded: the coder's worst case, 16 + 2^-13 bits per field of the
+ * fullest frame plus 2 (derivation in csrc/bitstream.hip). */
+FPC_API long long fpc_bitstream_bound(const int sizes[5], int entropy, int L);
+/* idx_dev [B,L,4] -> row b of bytes_dev from byte b * stride.  Bytes of the row past ceil(nbits / 8) are written as zero
+ * up to stride; nothing at or beyond stride is written.  nbits_dev[b] is the true bit count even where it exceeds
+ * 8 * stride (the coder keeps counting and stops storing: that is how a caller sees truncation); stride = 0 with a NULL
+ * bytes_dev asks for the sizes alone.  An utterance whose symbols contradict the layout -- an index >= its table size, a
+ * below-threshold symbol missing where a book exists, a symbol present where none is possible -- gets nbits = -1 and a
+ * zeroed row; the others are unaffected.  Asynchronous on the stream. */
+FPC_API int fpc_bitstream_pack(const int sizes[5], const fpc_entropy_models* models, const int32_t* idx_dev, int B, int L,
+                       uint8_t* bytes_dev, long long stride, int32_t* nbits_dev, fpc_stream s);
+/* The inverse: idx_dev [B,L,4] in fpc_encode's convention (-1 = not coded, the below-threshold scalar index offset by
+ * n_hi).  Bits past stride read as 0; nothing outside a row is read.  Symbols are not range-checked here
+ * (fpc_decode_features does that).  Asynchronous on the stream. */
+FPC_API int fpc_bitstream_unpack(const int sizes[5], const fpc_entropy_models* models, const uint8_t* bytes_dev,
+                         long long stride, int B, int L, int32_t* idx_dev, fpc_stream s);
 
 /* Stand-alone quantizers with the reference call shapes
  * (vq_quantize vq_func.py:134, scl_quantize vq_func.py:167).  Device pointers.
