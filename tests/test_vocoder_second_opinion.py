@@ -6,6 +6,7 @@ LPC synthesis), written straight from the Keras layer semantics with no regard f
 orders, table activations or tabulated embeddings, is teacher-forced along the oracle's own trace; with the
 same uniform numbers it must draw the same mu-law level at (practically) every sample."""
 import numpy as np
+import pytest
 
 
 def _sig(x):
@@ -47,17 +48,15 @@ def _condition(w, feat):
     return np.tanh(x @ w["dense2_kernel"].astype(np.float64) + w["dense2_bias"])
 
 
-def test_numpy_restatement_draws_what_the_oracle_draws(oracle, synth):
-    w = synth.lpcnet_weights()
+def _teacher_forced(oracle, w, feat, seed):
+    """the float64 restatement teacher-forced along the oracle's trace of one utterance: (draws identical, draws within
+    one level, draws, largest error of the frame-rate stack)"""
     W = {k: np.asarray(v, np.float64) for k, v in w.items()}
-    T, seed = 3, 4242
-    feat = synth.vocoder_features_raw(1, T, utt0=31)[0]
-    feat[:, 19] = [-0.2, 0.8, 0.5]                       # an unvoiced, a strongly and a mildly sharpened frame
-    feat[:, 20:] = oracle.ceps2lpc(feat[:, :20])[0]
+    T = feat.shape[0]
     orc = oracle.LPCNet(w)
     pcm, exc_o, pcm_f = orc.synthesize(feat, seed, trace=True)
     cf = _condition(w, feat)
-    assert np.abs(cf - orc.condition(feat)).max() < 2e-5    # frame-rate stack, float64 vs the oracle's float32 chains
+    cond_err = np.abs(cf - orc.condition(feat)).max()        # frame-rate stack, float64 vs the oracle's float32 chains
     s1, s2 = np.zeros(384), np.zeros(16)
     hist = np.zeros(T * 160 + 16)                            # hist[16 + t] = pcm[t]
     exc_prev, same, near, n = 128, 0, 0, 0
@@ -91,7 +90,38 @@ def test_numpy_restatement_draws_what_the_oracle_draws(oracle, synth):
         exc_prev = int(exc_o[t])
         hist[16 + t] = float(pcm_f[t])
         assert abs((pred + _ulaw2lin(exc_prev)) - float(pcm_f[t])) < 1e-2 * max(1.0, abs(float(pcm_f[t])))
+    return same, near, n, cond_err
+
+
+def test_numpy_restatement_draws_what_the_oracle_draws(oracle, synth):
+    w = synth.lpcnet_weights()
+    T, seed = 3, 4242
+    feat = synth.vocoder_features_raw(1, T, utt0=31)[0]
+    feat[:, 19] = [-0.2, 0.8, 0.5]                       # an unvoiced, a strongly and a mildly sharpened frame
+    feat[:, 20:] = oracle.ceps2lpc(feat[:, :20])[0]
+    same, near, n, cond_err = _teacher_forced(oracle, w, feat, seed)
+    assert cond_err < 2e-5
     print('second opinion:', same, 'of', n, 'draws identical,', near, 'within one level')
+    assert same >= 0.99 * n and near == n, (same, near, n)
+
+
+@pytest.mark.parametrize("name", ["ladder", "diagonal_crossing", "edge_of_408", "widest_group", "no_room_for_padding",
+                                  "skewed"])
+def test_numpy_restatement_on_the_packing_edge_patterns(oracle, synth, name):
+    """the same second opinion on recurrent matrices built at the edges of the block layout (tests/vocoder_patterns.py:
+    empty row groups, partly filled leaves, a 64-block group, skewed occupancy): the oracle's canonical tree over the
+    blocks of a row group has not seen these from synth.lpcnet_weights' random pruning either.  The float64 restatement
+    multiplies by the dense matrix and knows nothing of blocks.  Three frames, one voiced; the bounds of the test above."""
+    import vocoder_patterns
+    w, counts = vocoder_patterns.build(synth, name)
+    assert oracle.LPCNet(w).nblocks == counts.sum()       # the pattern the oracle sees is the pattern asked for
+    T, seed = 3, 4243
+    feat = synth.vocoder_features_raw(1, T, utt0=33)[0]
+    feat[:, 19] = [-0.2, 0.8, 0.1]
+    feat[:, 20:] = oracle.ceps2lpc(feat[:, :20])[0]
+    same, near, n, cond_err = _teacher_forced(oracle, w, feat, seed)
+    assert cond_err < 2e-5
+    print('second opinion,', name + ':', same, 'of', n, 'draws identical,', near, 'within one level')
     assert same >= 0.99 * n and near == n, (same, near, n)
 
 
