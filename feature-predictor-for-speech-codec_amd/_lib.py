@@ -23,6 +23,8 @@ SYMBOLS = [
     "fpc_cb_workspace_bytes", "fpc_cb_find_nearest", "fpc_cb_update", "fpc_cb_mean0", "fpc_kmeans1d",
     "fpc_entropy_models_create", "fpc_entropy_models_destroy", "fpc_bitstream_bound", "fpc_bitstream_pack",
     "fpc_bitstream_unpack",
+    "fpc_wavenet_create", "fpc_wavenet_destroy", "fpc_wavenet_workspace_bytes", "fpc_wavenet_synthesize",
+    "fpc_wavenet_forward", "fpc_wavenet_condition", "fpc_wavenet_last_decode_ms",
 ]
 
 
@@ -59,6 +61,24 @@ LPCNET_SHAPES = {
 
 class LpcnetWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LPCNET_KEYS]
+
+
+class WavenetConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in (
+        "out_channels", "num_blocks", "num_layers", "inp_channels", "residual_channels", "gate_channels",
+        "skip_channels", "kernel_size", "cin_channels", "cout_channels")] + [
+            ("upsample_scales", C.c_int * 2), ("causal", C.c_int), ("local", C.c_int), ("fat_upsampler", C.c_int),
+            ("nu", C.c_int)]
+
+
+WAVENET_KEYS = ["embedding", "c_conv0_w", "c_conv0_b", "c_conv1_w", "c_conv1_b", "c_fc0_w", "c_fc0_b", "c_fc1_w",
+                "c_fc1_b", "up0_w", "up0_b", "up1_w", "up1_b", "front_w", "front_b", "filter_w", "filter_b", "gate_w",
+                "gate_b", "filter_c_w", "filter_c_b", "gate_c_w", "gate_c_b", "res_w", "res_b", "skip_w", "skip_b",
+                "final1_w", "final1_b", "final2_w", "final2_b"]
+
+
+class WavenetWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in WAVENET_KEYS]
 
 
 def lib():
@@ -140,6 +160,19 @@ def lib():
                                          C.c_void_p, C.c_void_p]
         L.fpc_bitstream_unpack.argtypes = [sizes5, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p]
+        L.fpc_wavenet_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.fpc_wavenet_destroy.argtypes = [C.c_void_p]
+        L.fpc_wavenet_destroy.restype = None
+        L.fpc_wavenet_workspace_bytes.restype = C.c_longlong
+        L.fpc_wavenet_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.fpc_wavenet_synthesize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fpc_wavenet_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fpc_wavenet_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+        L.fpc_wavenet_last_decode_ms.restype = C.c_float
+        L.fpc_wavenet_last_decode_ms.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 

@@ -1,0 +1,170 @@
+"""The reference's own vocoder: the Gaussian-output WaveNet of src/models/wavenet.py, decoded by k_wn_decode
+(csrc/wavenet_decode.h) for a whole batch of utterances.  `Wavenet` takes the reference's constructor arguments and its
+state_dict, key for key; `generate_lpc`, `upsample` and `forward_stats` take the reference's tensor layouts."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+FRAME = 160
+
+
+def _folded(sd, name):
+    """weight of module `name`: weight_norm's (g, v) pair folded with torch's own operator, or a plain weight"""
+    for g, v in ((name + ".weight_g", name + ".weight_v"),
+                 (name + ".parametrizations.weight.original0", name + ".parametrizations.weight.original1")):
+        if g in sd:
+            return torch._weight_norm(torch.as_tensor(sd[v]).float(), torch.as_tensor(sd[g]).float(), 0)
+    return torch.as_tensor(sd[name + ".weight"]).float()
+
+
+class Wavenet:
+    def __init__(self, out_channels=1, num_blocks=3, num_layers=10, inp_channels=1, residual_channels=512,
+                 gate_channels=512, skip_channels=512, kernel_size=2, cin_channels=36, cout_channels=36,
+                 upsample_scales=None, causal=True, local=True, fat_upsampler=True, nu=0):
+        """wavenet.py:12-15; nu: utterances per workgroup (16, 32, 0 = chosen from the batch size).  Raises FpcError for a
+        configuration the kernel does not serve (fpc_wavenet_config in include/fpcodec.h)."""
+        scales = list(upsample_scales or [])
+        if len(scales) != 2:
+            raise _lib.FpcError(f"fpc_wavenet: upsample_scales = {scales}; only [10, 16] is built")
+        self.cfg = _lib.WavenetConfig(out_channels, num_blocks, num_layers, inp_channels, residual_channels, gate_channels,
+                                      skip_channels, kernel_size, cin_channels, cout_channels, (C.c_int * 2)(*scales),
+                                      int(causal), int(local), int(fat_upsampler), nu)
+        self.handle = None
+        self.w = None
+        self._ws = None
+        self._create(None)
+        self.nfeat = cin_channels - 64
+        self.layers = num_blocks * num_layers
+
+    def _create(self, weights):
+        h = C.c_void_p()
+        _lib.check(_lib.lib().fpc_wavenet_create(C.byref(self.cfg), C.byref(weights) if weights is not None else None, C.byref(h)),
+                   "fpc_wavenet_create")
+        self._destroy()
+        self.handle = h
+
+    def _destroy(self):
+        if self.handle is not None:
+            _lib.lib().fpc_wavenet_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self._destroy()
+        except Exception:
+            pass
+
+    def receptive_field_size(self):
+        return sum(2 ** (i % self.cfg.num_layers) for i in range(self.layers)) + 32
+
+    def load_state_dict(self, sd):
+        """the reference's own keys (torch tensors or arrays); weight_g / weight_v pairs are folded here"""
+        _lib.require_gpu()
+        c = self.cfg
+        R, G, S, co = c.residual_channels, c.gate_channels, c.skip_channels, c.cout_channels
+        t = lambda k: torch.as_tensor(sd[k]).float()
+        per_layer = lambda f: torch.stack([f(f"res_blocks.{n}.") for n in range(self.layers)])
+        w = {
+            "embedding": t("embedding.weight"),
+            "c_conv0_w": t("c_conv.0.weight"), "c_conv0_b": t("c_conv.0.bias"),
+            "c_conv1_w": t("c_conv.2.weight"), "c_conv1_b": t("c_conv.2.bias"),
+            "c_fc0_w": t("c_fc.0.weight"), "c_fc0_b": t("c_fc.0.bias"),
+            "c_fc1_w": t("c_fc.2.weight"), "c_fc1_b": t("c_fc.2.bias"),
+            "up0_w": _folded(sd, "upsample_conv.0"), "up0_b": t("upsample_conv.0.bias"),
+            "up1_w": _folded(sd, "upsample_conv.2"), "up1_b": t("upsample_conv.2.bias"),
+            "front_w": _folded(sd, "front_conv.0.conv"), "front_b": t("front_conv.0.conv.bias"),
+            "final1_w": _folded(sd, "final_conv.1.conv"), "final1_b": t("final_conv.1.conv.bias"),
+            "final2_w": _folded(sd, "final_conv.3.conv"), "final2_b": t("final_conv.3.conv.bias"),
+        }
+        for key, mod in (("filter", "filter_conv.conv"), ("gate", "gate_conv.conv"), ("filter_c", "filter_conv_c"),
+                         ("gate_c", "gate_conv_c"), ("res", "res_conv"), ("skip", "skip_conv")):
+            w[key + "_w"] = per_layer(lambda p: _folded(sd, p + mod))
+            w[key + "_b"] = per_layer(lambda p: t(p + mod + ".bias"))
+        L = self.layers
+        shapes = {"embedding": (256, 64), "c_conv0_w": (co, c.cin_channels, 3), "c_conv1_w": (co, co, 3),
+                  "c_fc0_w": (co, co), "c_fc1_w": (co, co), "up0_w": (1, 1, 3, 20), "up1_w": (1, 1, 3, 32),
+                  "front_w": (R, c.inp_channels, 32), "filter_w": (L, G, R, 2), "gate_w": (L, G, R, 2),
+                  "filter_c_w": (L, G, co, 1), "gate_c_w": (L, G, co, 1), "res_w": (L, R, G, 1), "skip_w": (L, S, G, 1),
+                  "final1_w": (S, S, 1), "final2_w": (2, S, 1)}
+        for k, s in shapes.items():
+            if tuple(w[k].shape) != s:
+                raise ValueError(f"{k}: shape {tuple(w[k].shape)} != {s}")
+        self.w = {k: np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32) for k, v in w.items()}
+        self._create(_lib.WavenetWeights(*[self.w[k].ctypes.data for k in _lib.WAVENET_KEYS]))
+        return self
+
+    # ---- calls ----
+    def workspace_bytes(self, B, T):
+        return int(_lib.lib().fpc_wavenet_workspace_bytes(self.handle, B, T))
+
+    def _workspace(self, B, T):
+        need = self.workspace_bytes(B, T)
+        if need < 0:
+            _lib.check(need, "fpc_wavenet_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        return self._ws
+
+    def _inputs(self, feat, periods, lpc):
+        """reference layouts -> the ABI's: feat (B,nfeat,L) -> [B,L,nfeat]; periods (B,L,1) or (B,L) int; lpc per sample
+        (B,160L,16), as synthesis.py:105 repeats it, or per frame (B,L,16)"""
+        f = torch.as_tensor(feat).to("cuda", torch.float32).transpose(1, 2).contiguous()
+        B, T, nf = f.shape
+        if nf != self.nfeat:
+            raise ValueError(f"feat has {nf} channels, the model takes {self.nfeat}")
+        p = torch.as_tensor(periods).to("cuda", torch.int32).reshape(B, T).contiguous()
+        a = None
+        if lpc is not None:
+            a = torch.as_tensor(lpc).to("cuda", torch.float32)
+            if a.shape[1] == T * FRAME:
+                a = a[:, ::FRAME]
+            a = a.reshape(B, T, 16).contiguous()
+        return f, p, a, B, T
+
+    def upsample(self, c, periods):
+        """wavenet.py:93-115: c (B,nfeat,L), periods (B,L,1) -> (B,cout,160L)"""
+        f, p, _, B, T = self._inputs(c, periods, None)
+        out = torch.empty(B, self.cfg.cout_channels, T * FRAME, device="cuda")
+        ws = self._workspace(B, T)
+        _lib.check(_lib.lib().fpc_wavenet_condition(self.handle, f.data_ptr(), p.data_ptr(), B, T, out.data_ptr(),
+                                                    ws.data_ptr(), _lib.stream_ptr()), "fpc_wavenet_condition")
+        return out
+
+    def generate_lpc(self, feat, periods, lpc, seeds=None, noise=None, return_x=False):
+        """wavenet.py:137-193 for a batch: (B,1,160L), the reference's x_out without its leading zero.  noise (B,160L):
+        the standard normal draws to use; else Philox keyed by seeds (B,) (default 0..B-1).  return_x: also the reference's x
+        buffer (the samples before line 188's filter), as a second (B,1,160L)."""
+        f, p, a, B, T = self._inputs(feat, periods, lpc)
+        if noise is not None:
+            noise = torch.as_tensor(noise).to("cuda", torch.float32).reshape(B, T * FRAME).contiguous()
+        sd = np.arange(B) if seeds is None else seeds
+        sd = torch.as_tensor(np.asarray(sd).astype(np.int64) if not torch.is_tensor(sd) else sd)
+        sd = sd.to("cuda", torch.int64).contiguous()
+        assert sd.numel() == B
+        out = torch.empty(B, 1, T * FRAME, device="cuda")
+        x = torch.empty_like(out) if return_x else None
+        ws = self._workspace(B, T)
+        _lib.check(_lib.lib().fpc_wavenet_synthesize(
+            self.handle, f.data_ptr(), p.data_ptr(), a.data_ptr(), B, T, sd.data_ptr(),
+            noise.data_ptr() if noise is not None else None, out.data_ptr(), x.data_ptr() if return_x else None,
+            ws.data_ptr(), _lib.stream_ptr()), "fpc_wavenet_synthesize")
+        return (out, x) if return_x else out
+
+    def forward_stats(self, x, feat, periods, lpc):
+        """teacher-forced: x (B,1,160L) or (B,160L) -> (B,2,160L), (mean, log_std) of every sample given the ones before
+        it -- Wavenet.forward on the inputs generate_lpc builds from x"""
+        f, p, a, B, T = self._inputs(feat, periods, lpc)
+        xs = torch.as_tensor(x).to("cuda", torch.float32).reshape(B, T * FRAME).contiguous()
+        st = torch.empty(B, T * FRAME, 2, device="cuda")
+        ws = self._workspace(B, T)
+        _lib.check(_lib.lib().fpc_wavenet_forward(self.handle, f.data_ptr(), p.data_ptr(), a.data_ptr(), B, T,
+                                                  xs.data_ptr(), st.data_ptr(), ws.data_ptr(), _lib.stream_ptr()),
+                   "fpc_wavenet_forward")
+        return st.transpose(1, 2)
+
+    def last_decode_ms(self):
+        return float(_lib.lib().fpc_wavenet_last_decode_ms(self.handle))

@@ -33,7 +33,9 @@ extern "C" {
  * 4: exports fpc_lpcnet_set_pairing and fpc_lpcnet_last_streams_per_workgroup (fpc_lpcnet_synthesize decodes two utterances
  *    per workgroup when the batch exceeds the device's compute units), fpc_lpcnet_paired_utterances and fpc_selftest.
  *    Added within 4 (new exports only, nothing existing changed; a binding written against the earlier set keeps working):
- *    fpc_entropy_models_create / _destroy, fpc_bitstream_bound, fpc_bitstream_pack, fpc_bitstream_unpack. */
+ *    fpc_entropy_models_create / _destroy, fpc_bitstream_bound, fpc_bitstream_pack, fpc_bitstream_unpack;
+ *    fpc_wavenet_create / _destroy, fpc_wavenet_workspace_bytes, fpc_wavenet_synthesize, fpc_wavenet_forward,
+ *    fpc_wavenet_condition, fpc_wavenet_last_decode_ms. */
 #define FPC_ABI_VERSION 4
 #define FPC_API __attribute__((visibility("default")))
 
@@ -357,6 +359,103 @@ FPC_API float fpc_lpcnet_last_decode_ms(fpc_lpcnet* m);
  * 100 * (partial-sum planes of the update/reset gates) + (planes of the candidate gate):
  * 208, 408 or 1616 ("sparse product").  <0 on a null handle. */
 FPC_API int fpc_lpcnet_kernel_variant(const fpc_lpcnet* m);
+
+/* ------------------------------------------------------------------------
+ * Gaussian WaveNet vocoder -- the reference's own sample-level model
+ * (src/models/wavenet.py, src/models/modules.py:10-86, driven by src/synthesis.py:36-125).
+ * Work split, LDS and register map: csrc/wavenet_decode.h, DESIGN.md.
+ * ---------------------------------------------------------------------- */
+/* The constructor arguments of Wavenet (wavenet.py:12-15) as src/synthesis.py:37-49 passes them.  Built: out_channels 2,
+ * kernel_size 2, causal, local = 0, fat_upsampler = 1, upsample_scales {10, 16}, inp_channels 1 or 3, cin_channels 84 or
+ * 100 (20 or 36 features + the 64 of the period embedding), R / G / S positive multiples of 16 -- anything else is
+ * FPC_ERR_INVALID.  R, G, S or cout_channels above 512, num_layers above 10 (a dilation above 512), or nu = 32 with a model
+ * whose activations exceed 160 KiB of LDS at that width: FPC_ERR_CAPACITY.  Both with text in fpc_last_error. */
+typedef struct {
+    int out_channels, num_blocks, num_layers, inp_channels;
+    int residual_channels, gate_channels, skip_channels, kernel_size;
+    int cin_channels, cout_channels;
+    int upsample_scales[2];
+    int causal, local, fat_upsampler;
+    int nu; /* utterances per workgroup: 16, 32, or 0 = chosen per call from the batch size */
+} fpc_wavenet_config;
+
+/* HOST pointers, torch layouts, weight_norm already folded (w = g v / |v|, torch._weight_norm).  Per-layer arrays hold the
+ * num_blocks * num_layers residual blocks back to back in res_blocks order. */
+typedef struct {
+    const float* embedding;  /* [256,64]                       embedding.weight */
+    const float* c_conv0_w;  /* [cout,cin,3]                   c_conv.0 */
+    const float* c_conv0_b;  /* [cout] */
+    const float* c_conv1_w;  /* [cout,cout,3]                  c_conv.2 */
+    const float* c_conv1_b;  /* [cout] */
+    const float* c_fc0_w;    /* [cout,cout] (out,in)           c_fc.0 */
+    const float* c_fc0_b;    /* [cout] */
+    const float* c_fc1_w;    /* [cout,cout]                    c_fc.2 */
+    const float* c_fc1_b;    /* [cout] */
+    const float* up0_w;      /* [3,20]  of (1,1,3,2*10)        upsample_conv.0 */
+    const float* up0_b;      /* [1] */
+    const float* up1_w;      /* [3,32]  of (1,1,3,2*16)        upsample_conv.2 */
+    const float* up1_b;      /* [1] */
+    const float* front_w;    /* [R,inp,32]                     front_conv.0.conv */
+    const float* front_b;    /* [R] */
+    const float* filter_w;   /* [layers,G,R,2]                 res_blocks.n.filter_conv.conv */
+    const float* filter_b;   /* [layers,G] */
+    const float* gate_w;     /* [layers,G,R,2]                 res_blocks.n.gate_conv.conv */
+    const float* gate_b;     /* [layers,G] */
+    const float* filter_c_w; /* [layers,G,cout]                res_blocks.n.filter_conv_c */
+    const float* filter_c_b; /* [layers,G] */
+    const float* gate_c_w;   /* [layers,G,cout]                res_blocks.n.gate_conv_c */
+    const float* gate_c_b;   /* [layers,G] */
+    const float* res_w;      /* [layers,R,G]                   res_blocks.n.res_conv */
+    const float* res_b;      /* [layers,R] */
+    const float* skip_w;     /* [layers,S,G]                   res_blocks.n.skip_conv */
+    const float* skip_b;     /* [layers,S] */
+    const float* final1_w;   /* [S,S]                          final_conv.1.conv */
+    const float* final1_b;   /* [S] */
+    const float* final2_w;   /* [2,S]                          final_conv.3.conv */
+    const float* final2_b;   /* [2] */
+} fpc_wavenet_weights;
+
+typedef struct fpc_wavenet fpc_wavenet;
+
+/* Wavenet.__init__ + load_state_dict (wavenet.py:12-81, synthesis.py:71-74): checks the configuration, packs the weights
+ * into the decode kernel's fragment order and uploads them.  w = NULL makes a handle of the shapes alone: it needs no
+ * device, serves fpc_wavenet_workspace_bytes, and every launch call refuses it. */
+FPC_API int fpc_wavenet_create(const fpc_wavenet_config* cfg, const fpc_wavenet_weights* w, fpc_wavenet** out);
+FPC_API void fpc_wavenet_destroy(fpc_wavenet* m);
+
+/* Bytes of device workspace the three calls below need for (B,T), with cout = cout_channels, R = residual_channels and
+ * D = num_blocks * (2^num_layers - 1), the sum of the dilations (a pure function, no device needed):
+ *   4 * ( Bp*cout*160*T  +  12*B*T*cout  +  Bp * R * D ),   Bp = ceil(B/32)*32
+ * the upsampled conditioning (c_upsampled of wavenet.py:149, kept per tile of utterances in time-major order so that a
+ * sample step reads one contiguous block), the frame-rate and 10x intermediates, and the dilation queues.  It grows with T: chunked passes are not built.  < 0: a negative fpc_status. */
+FPC_API long long fpc_wavenet_workspace_bytes(const fpc_wavenet* m, int B, int T);
+
+/* Wavenet.generate_lpc (wavenet.py:137-193) for B utterances at once, without its leading zero.  Device pointers:
+ *   feat [B,T,nfeat] float32 (time-major: the transpose of what the reference passes), periods [B,T] int32 (0..255),
+ *   lpc [B,T,16] per frame (the reference repeats each row 160 times, synthesis.py:105), seeds [B] uint64,
+ *   noise [B,160T] float32 standard normal draws or NULL (then Philox4x32-10 keyed by the seeds, wavenet_decode.h;
+ *   seeds may be NULL when noise is given), out [B,160T] float32: out[i] = 0.85 x[i-1] + x[i] (wavenet.py:188),
+ *   x [B,160T] float32 or NULL: the samples x themselves (the reference's x buffer, wavenet.py:183).
+ * With inp_channels = 3 the prediction channel holds pred of each position computed from that position's true history, which
+ * is what the reference's window holds except in its first 16 positions once i >= the receptive field (there utils.lpc_pred
+ * pads with zeros instead). */
+FPC_API int fpc_wavenet_synthesize(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* lpc_dev,
+                           int B, int T, const uint64_t* seeds_dev, const float* noise_dev, float* out_dev,
+                           float* x_dev, void* workspace_dev, fpc_stream s);
+
+/* Teacher-forced: Wavenet.forward (wavenet.py:83-91) on the inputs generate_lpc would build from a given x [B,160T]
+ * (wavenet.py:161-178): stats[b,i] = (mean, log_std) of sample i given x[..i-1].  Same kernel, no sampling. */
+FPC_API int fpc_wavenet_forward(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* lpc_dev,
+                        int B, int T, const float* x_dev, float* stats_dev, void* workspace_dev, fpc_stream s);
+
+/* Wavenet.upsample (wavenet.py:93-115): cfeat [B,cout,160T] */
+FPC_API int fpc_wavenet_condition(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, int B, int T,
+                          float* cfeat_dev, void* workspace_dev, fpc_stream s);
+
+/* duration (ms) of the last synthesize / forward call's sample-loop launch (the clearing of the queues included), measured
+ * with HIP events on the launch stream; synchronises on them.  <0 if none.  (The reference prints samples per second,
+ * wavenet.py:215-219.) */
+FPC_API float fpc_wavenet_last_decode_ms(fpc_wavenet* m);
 
 /* ---- predictor training step (src/train_frame.py:53-120, the live branch) ----
  * One step = teacher-forced Wavernn.forward over feat [B,L,in] (device), nn.MSELoss(out[:, :-1],
