@@ -13,11 +13,11 @@
 //   Y  s1' ready
 //        S: GRU_B -> s2'                           M: 6 of the 16 columns of the sparse product of s1'
 //   Z1 s2' ready
-//        S: dual FC -> 255 node probabilities      M: 4 more columns
+//        S: dual FC -> 255 node probabilities      M: 5 more columns
 //   Z2 q ready
 //        S wave 0 (unvoiced frame): 4 leaf probabilities per lane, tail cut, scan, draw, control block
 //        (voiced frame: all 256 sampler lanes compute leaf probability + sharpening, barrier Z3, then
-//         wave 0 normalises and draws)              M: last 6 columns, partial sums -> LDS
+//         wave 0 normalises and draws)              M: last 5 columns, partial sums -> LDS
 // The sparse product (61 % of the algorithmic FLOPs) is hidden completely under the sampler phases;
 // HBM is touched only for the gathered table rows (L2-resident), the per-frame conditioning rows and
 // 2 bytes of PCM per sample.
@@ -41,10 +41,13 @@ constexpr int PSTRIDE = GA + 4;
 #define FPC_NA 6  // sparse-product columns (of 16) computed under GRU_B ...
 #endif
 #ifndef FPC_PCM_WHERE
-#define FPC_PCM_WHERE 0  // de-emphasis + PCM store: 0 drawing wave behind barrier X, 1 drawing wave before it, 2 wave 3 behind it
+// de-emphasis + PCM store: 0 drawing wave behind barrier X, 1 drawing wave before it, 2 wave 3 behind it.  Wave 0 ends the
+// window phase X..Y (it starts it last: its draw ends ..X), so what it does behind barrier X is on the sample's critical
+// path; wave 3 waits 330 cycles in that phase (profiles/r06_phase_stamps.txt; the gain: r07_ablations.txt, -1.4 %)
+#define FPC_PCM_WHERE 2
 #endif
 #ifndef FPC_NB
-#define FPC_NB 4  // ... and under the dual FC; the rest runs under the draw
+#define FPC_NB 5  // ... and under the dual FC; the rest runs under the draw (5 with FPC_PCM_WHERE 2: a further -0.7 %)
 #endif
 
 struct DecodeParams {
@@ -407,7 +410,7 @@ __global__ __launch_bounds__(NTHREADS) void k_decode(const DecodeParams P) {
         for (int k = 0; k < 16; ++k) fcw[k] = mk2(P.lane_fc[k * NSAMP + sl], P.lane_fc[(16 + k) * NSAMP + sl]);
         fcw[16] = mk2(P.lane_fc[32 * NSAMP + sl], P.lane_fc[33 * NSAMP + sl]);
         fcw[17] = mk2(P.lane_fc[34 * NSAMP + sl], P.lane_fc[35 * NSAMP + sl]);
-        float mem = resume ? rec[RNN_A + 36] : 0.0f;     // de-emphasis state (tracked by every lane of the drawing wave)
+        float mem = resume ? rec[RNN_A + 36] : 0.0f;     // de-emphasis state (tracked by every lane of the wave FPC_PCM_WHERE names)
         float pcm_new = 0.0f; // the sample just drawn (drawing wave)
         float s2_own = resume ? rec[RNN_A + u] : 0.0f;  // state of unit u, replicated over the 16 lanes of its row
         if (P.state != nullptr) __syncthreads();  // (the mat-vec waves' product of the resumed state)
@@ -608,10 +611,8 @@ __global__ __launch_bounds__(NTHREADS) void k_decode(const DecodeParams P) {
                 rec[RNN_A + sl] = L.s2[sl];
                 rec[RNN_A + 16 + sl] = L.hist[sl];
             }
-            if (sl == 0) {
-                *reinterpret_cast<float4*>(&rec[RNN_A + 32]) = *reinterpret_cast<const float4*>(&L.o_sig);
-                rec[RNN_A + 36] = mem;
-            }
+            if (sl == 0) *reinterpret_cast<float4*>(&rec[RNN_A + 32]) = *reinterpret_cast<const float4*>(&L.o_sig);
+            if (sl == (FPC_PCM_WHERE == 2 ? 3 * 64 : 0)) rec[RNN_A + 36] = mem;  // (by the wave that tracks the de-emphasis state)
         }
     }
 }
