@@ -25,6 +25,8 @@ SYMBOLS = [
     "fpc_bitstream_unpack",
     "fpc_wavenet_create", "fpc_wavenet_destroy", "fpc_wavenet_workspace_bytes", "fpc_wavenet_synthesize",
     "fpc_wavenet_forward", "fpc_wavenet_condition", "fpc_wavenet_last_decode_ms",
+    "fpc_wavenet_forward_parallel", "fpc_wavenet_forward_input", "fpc_wavenet_forward_workspace_bytes",
+    "fpc_wavenet_set_forward_tile", "fpc_wavenet_forward_tile",
 ]
 
 
@@ -171,6 +173,13 @@ def lib():
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fpc_wavenet_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+        L.fpc_wavenet_forward_parallel.argtypes = L.fpc_wavenet_forward.argtypes
+        L.fpc_wavenet_forward_input.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fpc_wavenet_forward_workspace_bytes.restype = C.c_longlong
+        L.fpc_wavenet_forward_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.fpc_wavenet_set_forward_tile.argtypes = [C.c_void_p, C.c_int]
+        L.fpc_wavenet_forward_tile.argtypes = [C.c_void_p]
         L.fpc_wavenet_last_decode_ms.restype = C.c_float
         L.fpc_wavenet_last_decode_ms.argtypes = [C.c_void_p]
         _lib = L

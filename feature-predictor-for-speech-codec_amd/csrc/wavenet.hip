@@ -1,12 +1,12 @@
 // wavenet.hip -- the reference's own vocoder, the Gaussian-output WaveNet of src/models/wavenet.py, as a batched decoder
 // (gfx950).  Host side: configuration check, weight packing, the frame-rate conditioning kernels and the launches; the
-// sample loop is k_wn_decode (wavenet_decode.h).
+// sample loop is k_wn_decode (wavenet_decode.h), the time-parallel teacher-forced pass the k_wnf_* family (wavenet_forward.h).
 //
 // Conditioning (wavenet.py:93-115) runs once per call in plain HIP, one thread per output value: k_wn_frame is the
 // embedding + concatenation + Conv1d(3) / Linear + tanh at frame rate, k_wn_upsample one ConvTranspose2d(1,1,(3,2s)) +
 // LeakyReLU(0.4) stage.  The transposed convolution is two-dimensional: three taps run across the channel axis, so channel
 // ch of the output reads channels ch-1..ch+1 of the input, and every output time reads two input times.
-#include "wavenet_decode.h"
+#include "wavenet_forward.h"
 #include <algorithm>
 #include <new>
 
@@ -30,6 +30,7 @@ struct fpc_wavenet {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     int last_nu = 0;
+    int tn = 0;  // positions per workgroup of the time-parallel pass: 16, 32, 64, or 0 = the widest that fits
 };
 
 namespace {
@@ -261,6 +262,126 @@ int run_decode(fpc_wavenet* m, int B, int T, const Workspace& w, const float* lp
     return FPC_OK;
 }
 
+// ---- the time-parallel teacher-forced pass (wavenet_forward.h) ----
+
+// LDS of the widest of the three MFMA kernels at TN positions: the layer's BA + Z panels, the last stage's Z + O, the
+// front layer's inputs with their halo
+size_t fwd_lds_bytes(const fpc_wavenet_config& c, int coutp, int tn) {
+    const int rows = std::max(2 * c.residual_channels + coutp + c.gate_channels, 2 * c.skip_channels);
+    return std::max((size_t)rows * tn, (size_t)c.inp_channels * (tn + FRONT)) * sizeof(float);
+}
+
+int pick_tn(const fpc_wavenet* m) {
+    if (m->tn) return m->tn;
+    // By measurement (profiles/wavenet_forward.txt): at the configured shape 32 makes 63.7 % of the MFMA peak and 64 makes
+    // 58.8 %.  k_wnf_layer<32> stays within 64 VGPRs and 80 KiB, so two workgroups share a compute unit and one's staging and
+    // gating run under the other's MFMAs; <64> fills the LDS alone.  So 64 is never the automatic choice.
+    if (fwd_lds_bytes(m->c, m->coutp, 32) <= LDS_BYTES) return 32;
+    return 16;  // every model `validate` admits fits at 16: (2 * 512 + 512 + 512) * 16 floats = 128 KiB
+}
+
+struct FwdWorkspace {
+    Workspace c;  // cfeat [B][cout][N] and the conditioning's intermediates
+    float *h[2], *skip, *inp;
+};
+long long fwd_floats(const fpc_wavenet* m, long long B, long long T, FwdWorkspace* w, float* base) {
+    const long long N = 160 * T, cf = B * m->c.cout_channels * N, fr = B * T * m->c.cout_channels;
+    const long long h = B * m->c.residual_channels * N, sk = B * m->c.skip_channels * N, in = B * m->c.inp_channels * N;
+    if (w) {
+        w->c.cfeat = base;
+        w->c.fa = base + cf;
+        w->c.fb = w->c.fa + fr;
+        w->c.u1 = w->c.fb + fr;
+        w->c.ring = nullptr;
+        w->h[0] = w->c.u1 + 10 * fr;
+        w->h[1] = w->h[0] + h;
+        w->skip = w->h[1] + h;
+        w->inp = w->skip + sk;
+    }
+    return cf + 12 * fr + 2 * h + sk + in;
+}
+
+template <int TN>
+int launch_forward(const fpc_wavenet* m, ForwardParams p, const FwdWorkspace& w, hipStream_t st) {
+    const fpc_wavenet_config& c = m->c;
+    const unsigned grid = (unsigned)((long long)p.B * p.tiles);
+    const size_t lds_front = (size_t)p.inp * (TN + FRONT) * sizeof(float);
+    const size_t lds_layer = (size_t)(2 * p.R + p.coutp + p.G) * TN * sizeof(float);
+    const size_t lds_final = (size_t)2 * p.S * TN * sizeof(float);
+    FPC_HIP(hipFuncSetAttribute((const void*)k_wnf_layer<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer));
+    FPC_HIP(hipFuncSetAttribute((const void*)k_wnf_final<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_final));
+    p.hout = w.h[0];
+    k_wnf_front<TN><<<grid, THREADS, lds_front, st>>>(p);
+    const float4 *w1 = p.w1, *w2 = p.w2;
+    const float *b1 = p.b1, *b_res = p.b_res;
+    for (int n = 0; n < m->layers; ++n) {
+        p.w1 = w1 + (long long)n * (p.G / 16) * 2 * p.K1q * 64;
+        p.b1 = b1 + (long long)n * 2 * p.G;
+        p.w2 = w2 + (long long)n * ((p.R + p.S) / 16) * p.Gq * 64;
+        p.b_res = b_res + (long long)n * p.R;
+        p.dil = 1 << (n % c.num_layers);
+        p.first = n == 0;
+        p.last = n + 1 == m->layers;
+        p.hin = w.h[n & 1];
+        p.hout = w.h[(n + 1) & 1];
+        k_wnf_layer<TN><<<grid, THREADS, lds_layer, st>>>(p);
+    }
+    k_wnf_final<TN><<<grid, THREADS, lds_final, st>>>(p);
+    FPC_HIP(hipGetLastError());
+    return FPC_OK;
+}
+
+// x != null: the input channels are built from x and the LPC taps into the workspace; else `inp` holds the caller's own
+int run_forward(fpc_wavenet* m, const float* feat, const int* periods, const float* lpc, const float* x, const float* inp, int B,
+                int T, float* stats, void* workspace, hipStream_t st) {
+    const fpc_wavenet_config& c = m->c;
+    const int tn = pick_tn(m);
+    ForwardParams p{};
+    p.B = B;
+    p.T = T;
+    p.N = T * 160;
+    p.tiles = (p.N + tn - 1) / tn;
+    if ((long long)B * p.tiles > 0x7fffffffll) {
+        fpc::set_error("fpc_wavenet: B = %d, T = %d make more than 2^31 workgroups; chunked passes are not built", B, T);
+        return FPC_ERR_CAPACITY;
+    }
+    FwdWorkspace w;
+    fwd_floats(m, B, T, &w, static_cast<float*>(workspace));
+    const int rc = run_condition(m, feat, periods, B, T, w.c.cfeat, 0, w.c, st);
+    if (rc != FPC_OK) return rc;
+    p.R = c.residual_channels;
+    p.G = c.gate_channels;
+    p.S = c.skip_channels;
+    p.cout = c.cout_channels;
+    p.coutp = m->coutp;
+    p.inp = c.inp_channels;
+    p.K0q = c.inp_channels * FRONT / 16;
+    p.K1q = (2 * p.R + p.coutp) / 16;
+    p.Gq = p.G / 16;
+    p.Sq = p.S / 16;
+    p.w_front = m->w_front.as<float4>();
+    p.b_front = m->b_front.as<float>();
+    p.w1 = m->w1.as<float4>();
+    p.b1 = m->b1.as<float>();
+    p.w2 = m->w2.as<float4>();
+    p.b_res = m->b_res.as<float>();
+    p.b_skip = m->b_skip.as<float>();
+    p.w_f1 = m->w_f1.as<float4>();
+    p.b_f1 = m->b_f1.as<float>();
+    p.w_f2 = m->w_f2.as<float4>();
+    p.b_f2[0] = m->b_f2[0];
+    p.b_f2[1] = m->b_f2[1];
+    p.x = x;
+    p.lpc = lpc;
+    p.inp_out = w.inp;
+    p.inp_in = x ? w.inp : inp;
+    p.cfeat = w.c.cfeat;
+    p.skip = w.skip;
+    p.stats = stats;
+    if (x) k_wnf_inputs<<<(unsigned)std::min<long long>(((long long)B * p.N + 255) / 256, 1 << 20), 256, 0, st>>>(p);
+    return tn == 64 ? launch_forward<64>(m, p, w, st) : tn == 32 ? launch_forward<32>(m, p, w, st) : launch_forward<16>(m, p, w, st);
+}
+
 }  // namespace
 
 extern "C" void fpc_wavenet_destroy(fpc_wavenet* m) {
@@ -435,6 +556,47 @@ extern "C" int fpc_wavenet_forward(fpc_wavenet* m, const float* feat_dev, const 
     const int rc2 = run_condition(m, feat_dev, periods_dev, B, T, w.cfeat, pick_nu(m, B), w, st);
     if (rc2 != FPC_OK) return rc2;
     return run_decode(m, B, T, w, lpc_dev, nullptr, nullptr, x_dev, nullptr, nullptr, stats_dev, st);
+}
+
+extern "C" long long fpc_wavenet_forward_workspace_bytes(const fpc_wavenet* m, int B, int T) {
+    if (!m || B < 1 || T < 1) {
+        fpc::set_error("fpc_wavenet_forward_workspace_bytes: null handle or B, T < 1");
+        return FPC_ERR_INVALID;
+    }
+    return 4 * fwd_floats(m, B, T, nullptr, nullptr);
+}
+
+extern "C" int fpc_wavenet_set_forward_tile(fpc_wavenet* m, int tn) {
+    FPC_REQUIRE(m != nullptr, "fpc_wavenet_set_forward_tile: null handle");
+    FPC_REQUIRE(tn == 0 || tn == 16 || tn == 32 || tn == 64, "fpc_wavenet_set_forward_tile: tn = %d, not 0, 16, 32 or 64", tn);
+    if (tn && fwd_lds_bytes(m->c, m->coutp, tn) > LDS_BYTES) {
+        fpc::set_error("fpc_wavenet_set_forward_tile: tn = %d needs %zu bytes of LDS for this model, the device has %zu", tn,
+                       fwd_lds_bytes(m->c, m->coutp, tn), LDS_BYTES);
+        return FPC_ERR_CAPACITY;
+    }
+    m->tn = tn;
+    return FPC_OK;
+}
+
+extern "C" int fpc_wavenet_forward_tile(const fpc_wavenet* m) { return m ? pick_tn(m) : (int)FPC_ERR_INVALID; }
+
+extern "C" int fpc_wavenet_forward_parallel(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev,
+                                            const float* lpc_dev, int B, int T, const float* x_dev, float* stats_dev,
+                                            void* workspace_dev, fpc_stream s) {
+    const int rc = check_call(m, B, T, workspace_dev);
+    if (rc != FPC_OK) return rc;
+    FPC_REQUIRE(feat_dev && periods_dev && lpc_dev && x_dev && stats_dev, "fpc_wavenet_forward_parallel: null pointer");
+    return run_forward(m, feat_dev, periods_dev, lpc_dev, x_dev, nullptr, B, T, stats_dev, workspace_dev,
+                       static_cast<hipStream_t>(s));
+}
+
+extern "C" int fpc_wavenet_forward_input(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* inp_dev,
+                                         int B, int T, float* stats_dev, void* workspace_dev, fpc_stream s) {
+    const int rc = check_call(m, B, T, workspace_dev);
+    if (rc != FPC_OK) return rc;
+    FPC_REQUIRE(feat_dev && periods_dev && inp_dev && stats_dev, "fpc_wavenet_forward_input: null pointer");
+    return run_forward(m, feat_dev, periods_dev, nullptr, nullptr, inp_dev, B, T, stats_dev, workspace_dev,
+                       static_cast<hipStream_t>(s));
 }
 
 extern "C" float fpc_wavenet_last_decode_ms(fpc_wavenet* m) {

@@ -126,6 +126,11 @@ __device__ __forceinline__ float tanh_e(float x) {
 }
 __device__ __forceinline__ float sigmoid_e(float x) { return 1.0f / (1.0f + fpc_expf(-x)); }
 
+// one tap of the prediction's sum (utils.py:91-114): s = 0, then k ascending over the 16 taps, pred = -s.  The sample loop and
+// k_wnf_inputs (wavenet_forward.h) both compile this expression.  (The whole loop in a shared function changed the register
+// allocation of k_wn_decode<32>; the tap alone leaves both instances' code as it was.)
+__device__ __forceinline__ float lpc_tap(float s, float a, float x) { return s + a * x; }
+
 // acc[a][nt] += A_a[16 x 16 KQ] . B[16 KQ x 16 nt..]: NA weight tiles against the same B fragments.  `row` maps a K index to
 // its panel row.
 template <int NA, int NT, class RowFn>
@@ -206,7 +211,7 @@ __global__ __launch_bounds__(THREADS) void k_wn_decode(const DecodeParams p) {
             }
             float s = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) s = s + lp_col[k * 16] * xh_col[((i - k) & 31) * 16];  // x(i-1-k) sits at position i-k
+            for (int k = 0; k < 16; ++k) s = lpc_tap(s, lp_col[k * 16], xh_col[((i - k) & 31) * 16]);  // x(i-1-k) sits at position i-k
             pred = -s;
             if (p.inp == 3) xh_col[(2 * FRONT + (i & 31)) * 16] = pred;
         }

@@ -1,6 +1,7 @@
 """The reference's own vocoder: the Gaussian-output WaveNet of src/models/wavenet.py, decoded by k_wn_decode
-(csrc/wavenet_decode.h) for a whole batch of utterances.  `Wavenet` takes the reference's constructor arguments and its
-state_dict, key for key; `generate_lpc`, `upsample` and `forward_stats` take the reference's tensor layouts."""
+(csrc/wavenet_decode.h) for a whole batch of utterances, and evaluated teacher-forced over all positions at once by the k_wnf_*
+kernels (csrc/wavenet_forward.h).  `Wavenet` takes the reference's constructor arguments and its
+state_dict, key for key; `forward`, `generate_lpc`, `upsample` and `forward_stats` take the reference's tensor layouts."""
 import ctypes as C
 
 import numpy as np
@@ -23,8 +24,9 @@ def _folded(sd, name):
 class Wavenet:
     def __init__(self, out_channels=1, num_blocks=3, num_layers=10, inp_channels=1, residual_channels=512,
                  gate_channels=512, skip_channels=512, kernel_size=2, cin_channels=36, cout_channels=36,
-                 upsample_scales=None, causal=True, local=True, fat_upsampler=True, nu=0):
-        """wavenet.py:12-15; nu: utterances per workgroup (16, 32, 0 = chosen from the batch size).  Raises FpcError for a
+                 upsample_scales=None, causal=True, local=True, fat_upsampler=True, nu=0, tn=0):
+        """wavenet.py:12-15; nu: utterances per workgroup of the sample loop (16, 32, 0 = chosen from the batch size); tn:
+        positions per workgroup of the time-parallel pass (16, 32, 64, 0 = 32 where it fits the LDS, else 16).  Raises FpcError for a
         configuration the kernel does not serve (fpc_wavenet_config in include/fpcodec.h)."""
         scales = list(upsample_scales or [])
         if len(scales) != 2:
@@ -35,6 +37,8 @@ class Wavenet:
         self.handle = None
         self.w = None
         self._ws = None
+        self._fws = None
+        self.tn = tn
         self._create(None)
         self.nfeat = cin_channels - 64
         self.layers = num_blocks * num_layers
@@ -45,6 +49,7 @@ class Wavenet:
                    "fpc_wavenet_create")
         self._destroy()
         self.handle = h
+        _lib.check(_lib.lib().fpc_wavenet_set_forward_tile(h, self.tn), "fpc_wavenet_set_forward_tile")
 
     def _destroy(self):
         if self.handle is not None:
@@ -109,6 +114,26 @@ class Wavenet:
             self._ws = torch.empty(need, dtype=torch.uint8, device="cuda")
         return self._ws
 
+    def forward_workspace_bytes(self, B, T):
+        return int(_lib.lib().fpc_wavenet_forward_workspace_bytes(self.handle, B, T))
+
+    def set_forward_tile(self, tn):
+        _lib.check(_lib.lib().fpc_wavenet_set_forward_tile(self.handle, tn), "fpc_wavenet_set_forward_tile")
+        self.tn = tn
+
+    def forward_tile(self):
+        """positions per workgroup the time-parallel pass runs with"""
+        return int(_lib.lib().fpc_wavenet_forward_tile(self.handle))
+
+    def _forward_workspace(self, B, T):
+        need = self.forward_workspace_bytes(B, T)
+        if need < 0:
+            _lib.check(need, "fpc_wavenet_forward_workspace_bytes")
+        if self._fws is None or self._fws.numel() < need:
+            self._fws = None
+            self._fws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        return self._fws
+
     def _inputs(self, feat, periods, lpc):
         """reference layouts -> the ABI's: feat (B,nfeat,L) -> [B,L,nfeat]; periods (B,L,1) or (B,L) int; lpc per sample
         (B,160L,16), as synthesis.py:105 repeats it, or per frame (B,L,16)"""
@@ -154,12 +179,35 @@ class Wavenet:
             ws.data_ptr(), _lib.stream_ptr()), "fpc_wavenet_synthesize")
         return (out, x) if return_x else out
 
-    def forward_stats(self, x, feat, periods, lpc):
+    def forward(self, x, periods, c):
+        """wavenet.py:83-91: x (B,inp_channels,160L), the net's own input channels, periods (B,L,1), c (B,nfeat,L) ->
+        (B,2,160L).  All positions at once (k_wnf_*)."""
+        f, p, _, B, T = self._inputs(c, periods, None)
+        xs = torch.as_tensor(x).to("cuda", torch.float32).contiguous()
+        if tuple(xs.shape) != (B, self.cfg.inp_channels, T * FRAME):
+            raise ValueError(f"x has shape {tuple(xs.shape)}, not {(B, self.cfg.inp_channels, T * FRAME)}")
+        st = torch.empty(B, T * FRAME, 2, device="cuda")
+        ws = self._forward_workspace(B, T)
+        _lib.check(_lib.lib().fpc_wavenet_forward_input(self.handle, f.data_ptr(), p.data_ptr(), xs.data_ptr(), B, T,
+                                                        st.data_ptr(), ws.data_ptr(), _lib.stream_ptr()),
+                   "fpc_wavenet_forward_input")
+        return st.transpose(1, 2)
+
+    __call__ = forward
+
+    def forward_stats(self, x, feat, periods, lpc, time_parallel=False):
         """teacher-forced: x (B,1,160L) or (B,160L) -> (B,2,160L), (mean, log_std) of every sample given the ones before
-        it -- Wavenet.forward on the inputs generate_lpc builds from x"""
+        it -- Wavenet.forward on the inputs generate_lpc builds from x.  time_parallel: all positions at once (k_wnf_*)
+        instead of the sample loop; the same values bit for bit."""
         f, p, a, B, T = self._inputs(feat, periods, lpc)
         xs = torch.as_tensor(x).to("cuda", torch.float32).reshape(B, T * FRAME).contiguous()
         st = torch.empty(B, T * FRAME, 2, device="cuda")
+        if time_parallel:
+            ws = self._forward_workspace(B, T)
+            _lib.check(_lib.lib().fpc_wavenet_forward_parallel(self.handle, f.data_ptr(), p.data_ptr(), a.data_ptr(), B, T,
+                                                               xs.data_ptr(), st.data_ptr(), ws.data_ptr(),
+                                                               _lib.stream_ptr()), "fpc_wavenet_forward_parallel")
+            return st.transpose(1, 2)
         ws = self._workspace(B, T)
         _lib.check(_lib.lib().fpc_wavenet_forward(self.handle, f.data_ptr(), p.data_ptr(), a.data_ptr(), B, T,
                                                   xs.data_ptr(), st.data_ptr(), ws.data_ptr(), _lib.stream_ptr()),

@@ -35,7 +35,9 @@ extern "C" {
  *    Added within 4 (new exports only, nothing existing changed; a binding written against the earlier set keeps working):
  *    fpc_entropy_models_create / _destroy, fpc_bitstream_bound, fpc_bitstream_pack, fpc_bitstream_unpack;
  *    fpc_wavenet_create / _destroy, fpc_wavenet_workspace_bytes, fpc_wavenet_synthesize, fpc_wavenet_forward,
- *    fpc_wavenet_condition, fpc_wavenet_last_decode_ms. */
+ *    fpc_wavenet_condition, fpc_wavenet_last_decode_ms;
+ *    fpc_wavenet_forward_parallel, fpc_wavenet_forward_input, fpc_wavenet_forward_workspace_bytes,
+ *    fpc_wavenet_set_forward_tile, fpc_wavenet_forward_tile. */
 #define FPC_ABI_VERSION 4
 #define FPC_API __attribute__((visibility("default")))
 
@@ -447,6 +449,33 @@ FPC_API int fpc_wavenet_synthesize(fpc_wavenet* m, const float* feat_dev, const 
  * (wavenet.py:161-178): stats[b,i] = (mean, log_std) of sample i given x[..i-1].  Same kernel, no sampling. */
 FPC_API int fpc_wavenet_forward(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* lpc_dev,
                         int B, int T, const float* x_dev, float* stats_dev, void* workspace_dev, fpc_stream s);
+
+/* The same teacher-forced pass, time-parallel (csrc/wavenet_forward.h): with x known every layer of Wavenet.forward
+ * (wavenet.py:83-91; modules.py:62-77) is a dense product over all 160T positions, run as one launch per layer with time on
+ * the N side of the MFMA.  Same arguments and meaning as fpc_wavenet_forward, and the same stats bit for bit; the workspace is
+ * the one fpc_wavenet_forward_workspace_bytes sizes. */
+FPC_API int fpc_wavenet_forward_parallel(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev,
+                                 const float* lpc_dev, int B, int T, const float* x_dev, float* stats_dev,
+                                 void* workspace_dev, fpc_stream s);
+
+/* Wavenet.forward(x, periods, c) proper (wavenet.py:83-91, local = False) on the caller's own input channels
+ * inp [B,inp_channels,160T] (position p holds what the net sees at p: wavenet.py:37-40 pads 31 zeros before it), feat and
+ * periods as above: stats [B,160T,2].  Time-parallel; workspace of fpc_wavenet_forward_workspace_bytes. */
+FPC_API int fpc_wavenet_forward_input(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* inp_dev,
+                              int B, int T, float* stats_dev, void* workspace_dev, fpc_stream s);
+
+/* Bytes of device workspace of the two calls above for (B,T), N = 160T (a pure function, serves a shape-only handle):
+ *   4 * ( B*cout*N + 12*B*T*cout + 2*B*R*N + B*S*N + B*inp_channels*N )
+ * the upsampled conditioning [B,cout,N] (c of wavenet.py:85) and its intermediates, the two alternating layer inputs
+ * (modules.py:77's output), the running skip sum (wavenet.py:46-48) and the input channels.  Linear in B*T; a pass is not
+ * chunked, and a (B,T) of more than 2^31 time tiles is FPC_ERR_CAPACITY at the call.  < 0: a negative fpc_status. */
+FPC_API long long fpc_wavenet_forward_workspace_bytes(const fpc_wavenet* m, int B, int T);
+
+/* Positions per workgroup of the time-parallel pass (the N extent of its MFMA tiles; wavenet.py:83-91 has no counterpart):
+ * tn = 16, 32 or 64, or 0 = automatic: 32 where its panels fit the 160 KiB of LDS (the fastest measured at the configured
+ * shape, where two such workgroups share a compute unit), else 16.  The result does not depend on it.  FPC_ERR_CAPACITY if the model's panels do not fit at tn.  _forward_tile: the width in effect. */
+FPC_API int fpc_wavenet_set_forward_tile(fpc_wavenet* m, int tn);
+FPC_API int fpc_wavenet_forward_tile(const fpc_wavenet* m);
 
 /* Wavenet.upsample (wavenet.py:93-115): cfeat [B,cout,160T] */
 FPC_API int fpc_wavenet_condition(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, int B, int T,

@@ -6,6 +6,11 @@ the receptive field for every sample as wavenet.py:154-191 does, 200 samples at 
 
     python tools/time_wavenet.py [--out profiles/wavenet_decode.txt] [--reps 3] [--frames 10]
 
+--forward times the teacher-forced pass instead: forward_stats through the sample loop (T = 10) against the time-parallel
+k_wnf_* pass with TN = 32 and 64, T = 10 and 300, B = 16 and 256, device events around the whole call.
+
+    python tools/time_wavenet.py --forward [--out profiles/wavenet_forward.txt] [--reps 3]
+
 Operations and bytes are computed from the shapes here; the peak is the 157.3 TFLOP/s f32 MFMA figure DESIGN.md quotes."""
 import argparse
 import os
@@ -86,16 +91,76 @@ def naive_loop(sd, c, rf, samples):
     return samples / (time.perf_counter() - t0)
 
 
+def forward_leg(a, mac):
+    """forward_stats teacher-forced: the sample loop (T = 10 only) against the time-parallel pass, each TN instance; device
+    events around the whole call (conditioning and input channels included), one warm-up"""
+    sd = state_dict()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lines = [f"Wavenet.forward_stats on {torch.cuda.get_device_name(0)} ({cus} CUs), R/G/S {R}/{G}/{S}, cout {CO}, {NB} x {NL} layers, "
+             f"inp_channels 1; {a.reps} timed calls after one warm-up, device events around the call",
+             f"MAC per position and utterance {mac}; TN = positions per workgroup of k_wnf_*, automatic choice "
+             f"{model(sd, 0).forward_tile()}; 'loop' = the sequential k_wn_decode with xin set",
+             "  path      B     T   positions   ms (min / median)     positions/s   TFLOP/s  of f32 MFMA peak   vs loop"]
+
+    def timed(fn):
+        ms = []
+        for r in range(a.reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        assert bool(torch.isfinite(out).all())
+        return min(ms[1:]), float(np.median(ms[1:])), out
+
+    models = {tn: model(sd, 0) for tn in (32, 64)}
+    for tn, m in models.items():
+        m.set_forward_tile(tn)
+    for T in (10, 300):
+        for B in (16, 256):
+            g = torch.Generator().manual_seed(B + T)
+            feat, per = torch.randn(B, NFEAT, T, generator=g).cuda(), torch.randint(0, 256, (B, T, 1), generator=g).cuda()
+            lpc = torch.randn(B, T, 16, generator=g)
+            lpc = (0.9 * lpc / lpc.abs().sum(-1, keepdim=True)).cuda()
+            x = (0.3 * torch.randn(B, 160 * T, generator=g)).cuda()
+            npos, loop_ms, loop_out = B * 160 * T, None, None
+            legs = ([("loop", lambda: models[64].forward_stats(x, feat, per, lpc))] if T == 10 else []) + \
+                   [(f"TN={tn}", lambda m=m: m.forward_stats(x, feat, per, lpc, time_parallel=True)) for tn, m in models.items()]
+            for name, fn in legs:
+                lo, med, out = timed(fn)
+                if name == "loop":
+                    loop_ms, loop_out = lo, out
+                elif loop_out is not None:
+                    assert torch.equal(out, loop_out), "time-parallel stats differ from the sample loop's"
+                rate = npos / (lo * 1e-3)
+                lines.append(f"{name:>6s} {B:6d} {T:5d} {npos:11d} {lo:10.2f} / {med:<10.2f} {rate:13.0f} {2 * mac * rate / 1e12:9.2f} "
+                             f"{100 * 2 * mac * rate / PEAK:10.2f} %" + (f"  {loop_ms / lo:10.1f} x" if loop_ms and name != "loop" else ""))
+                print(lines[-1], flush=True)
+                del out
+            for m in models.values():  # the 25 GB of the largest shape are not kept
+                m._fws = m._ws = None
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/wavenet_decode.txt")
+    ap.add_argument("--out", default=None, help="default profiles/wavenet_decode.txt, with --forward profiles/wavenet_forward.txt")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--frames", type=int, default=10)
+    ap.add_argument("--forward", action="store_true", help="time the teacher-forced pass instead of the sample loop")
     a = ap.parse_args()
+    a.out = a.out or ("profiles/wavenet_forward.txt" if a.forward else "profiles/wavenet_decode.txt")
     _lib.require_gpu()
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     T, N, L = a.frames, a.frames * 160, NB * NL
     mac = R * 32 + L * (2 * G * (2 * R + CO) + (R + S) * G) - R * G + S * S + 2 * S
+    if a.forward:
+        lines = forward_leg(a, mac)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     wbytes = 4 * (R * 32 + L * (2 * G * (2 * R + CO) + (R + S) * G) - R * G + S * S + 16 * S)
     sd = state_dict()
     lines = [f"k_wn_decode on {torch.cuda.get_device_name(0)} ({cus} CUs), R/G/S {R}/{G}/{S}, cout {CO}, {NB} x {NL} layers, "
