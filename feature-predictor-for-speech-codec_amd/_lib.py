@@ -27,6 +27,8 @@ SYMBOLS = [
     "fpc_wavenet_forward", "fpc_wavenet_condition", "fpc_wavenet_last_decode_ms",
     "fpc_wavenet_forward_parallel", "fpc_wavenet_forward_input", "fpc_wavenet_forward_workspace_bytes",
     "fpc_wavenet_set_forward_tile", "fpc_wavenet_forward_tile",
+    "fpc_wavenet_loss_backward", "fpc_wavenet_backward_workspace_bytes", "fpc_wavenet_backward_stats_offset",
+    "fpc_wavenet_set_backward_tile", "fpc_wavenet_backward_tile",
 ]
 
 
@@ -81,6 +83,14 @@ WAVENET_KEYS = ["embedding", "c_conv0_w", "c_conv0_b", "c_conv1_w", "c_conv1_b",
 
 class WavenetWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in WAVENET_KEYS]
+
+
+# fpc_wavenet_grads: the sample-level members of WAVENET_KEYS, then the upsampled conditioning
+WAVENET_GRAD_KEYS = WAVENET_KEYS[WAVENET_KEYS.index("front_w"):] + ["cfeat"]
+
+
+class WavenetGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in WAVENET_GRAD_KEYS]
 
 
 def lib():
@@ -182,6 +192,12 @@ def lib():
         L.fpc_wavenet_forward_tile.argtypes = [C.c_void_p]
         L.fpc_wavenet_last_decode_ms.restype = C.c_float
         L.fpc_wavenet_last_decode_ms.argtypes = [C.c_void_p]
+        L.fpc_wavenet_loss_backward.argtypes = [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 4
+        for f in (L.fpc_wavenet_backward_workspace_bytes, L.fpc_wavenet_backward_stats_offset):
+            f.restype = C.c_longlong
+            f.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.fpc_wavenet_set_backward_tile.argtypes = [C.c_void_p, C.c_int]
+        L.fpc_wavenet_backward_tile.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 

@@ -1,12 +1,13 @@
 // wavenet.hip -- the reference's own vocoder, the Gaussian-output WaveNet of src/models/wavenet.py, as a batched decoder
 // (gfx950).  Host side: configuration check, weight packing, the frame-rate conditioning kernels and the launches; the
-// sample loop is k_wn_decode (wavenet_decode.h), the time-parallel teacher-forced pass the k_wnf_* family (wavenet_forward.h).
+// sample loop is k_wn_decode (wavenet_decode.h), the time-parallel teacher-forced pass the k_wnf_* family (wavenet_forward.h),
+// the loss and the backward pass the k_wnb_* family (wavenet_backward.h).
 //
 // Conditioning (wavenet.py:93-115) runs once per call in plain HIP, one thread per output value: k_wn_frame is the
 // embedding + concatenation + Conv1d(3) / Linear + tanh at frame rate, k_wn_upsample one ConvTranspose2d(1,1,(3,2s)) +
 // LeakyReLU(0.4) stage.  The transposed convolution is two-dimensional: three taps run across the channel axis, so channel
 // ch of the output reads channels ch-1..ch+1 of the input, and every output time reads two input times.
-#include "wavenet_forward.h"
+#include "wavenet_backward.h"
 #include <algorithm>
 #include <new>
 
@@ -31,6 +32,8 @@ struct fpc_wavenet {
     bool timed = false;
     int last_nu = 0;
     int tn = 0;  // positions per workgroup of the time-parallel pass: 16, 32, 64, or 0 = the widest that fits
+    fpc::DevBuf w1t, w2t, w_f1t, f2;  // the backward pass's transposed A operands, and final2_w plain
+    int btn = 0;                      // positions per workgroup of k_wnb_final / k_wnb_layer: 16, 32 or 0 = automatic
 };
 
 namespace {
@@ -301,16 +304,19 @@ long long fwd_floats(const fpc_wavenet* m, long long B, long long T, FwdWorkspac
     return cf + 12 * fr + 2 * h + sk + in;
 }
 
-template <int TN>
-int launch_forward(const fpc_wavenet* m, ForwardParams p, const FwdWorkspace& w, hipStream_t st) {
+// SAVE: the pass before a backward; hs = the layers' inputs, one [B][R][N] buffer each, ts = their t, s [B][2G][N] each
+template <int TN, bool SAVE = false>
+int launch_forward(const fpc_wavenet* m, ForwardParams p, const FwdWorkspace& w, hipStream_t st, float* hs = nullptr,
+                   float* ts = nullptr) {
     const fpc_wavenet_config& c = m->c;
     const unsigned grid = (unsigned)((long long)p.B * p.tiles);
     const size_t lds_front = (size_t)p.inp * (TN + FRONT) * sizeof(float);
     const size_t lds_layer = (size_t)(2 * p.R + p.coutp + p.G) * TN * sizeof(float);
     const size_t lds_final = (size_t)2 * p.S * TN * sizeof(float);
-    FPC_HIP(hipFuncSetAttribute((const void*)k_wnf_layer<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer));
-    FPC_HIP(hipFuncSetAttribute((const void*)k_wnf_final<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_final));
-    p.hout = w.h[0];
+    FPC_HIP(hipFuncSetAttribute((const void*)k_wnf_layer<TN, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer));
+    FPC_HIP(hipFuncSetAttribute((const void*)k_wnf_final<TN, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_final));
+    const long long hsz = (long long)p.B * p.R * p.N;
+    p.hout = SAVE ? hs : w.h[0];
     k_wnf_front<TN><<<grid, THREADS, lds_front, st>>>(p);
     const float4 *w1 = p.w1, *w2 = p.w2;
     const float *b1 = p.b1, *b_res = p.b_res;
@@ -322,21 +328,19 @@ int launch_forward(const fpc_wavenet* m, ForwardParams p, const FwdWorkspace& w,
         p.dil = 1 << (n % c.num_layers);
         p.first = n == 0;
         p.last = n + 1 == m->layers;
-        p.hin = w.h[n & 1];
-        p.hout = w.h[(n + 1) & 1];
-        k_wnf_layer<TN><<<grid, THREADS, lds_layer, st>>>(p);
+        p.hin = SAVE ? hs + n * hsz : w.h[n & 1];
+        p.hout = SAVE ? hs + (n + 1 < m->layers ? n + 1 : 0) * hsz : w.h[(n + 1) & 1];  // the last block stores no h
+        if (SAVE) p.ts = ts + (long long)n * 2 * p.G * p.B * p.N;
+        k_wnf_layer<TN, SAVE><<<grid, THREADS, lds_layer, st>>>(p);
     }
-    k_wnf_final<TN><<<grid, THREADS, lds_final, st>>>(p);
+    k_wnf_final<TN, SAVE><<<grid, THREADS, lds_final, st>>>(p);
     FPC_HIP(hipGetLastError());
     return FPC_OK;
 }
 
-// x != null: the input channels are built from x and the LPC taps into the workspace; else `inp` holds the caller's own
-int run_forward(fpc_wavenet* m, const float* feat, const int* periods, const float* lpc, const float* x, const float* inp, int B,
-                int T, float* stats, void* workspace, hipStream_t st) {
+// the shape and weight members of the forward's parameters
+int forward_params(const fpc_wavenet* m, int B, int T, int tn, ForwardParams& p) {
     const fpc_wavenet_config& c = m->c;
-    const int tn = pick_tn(m);
-    ForwardParams p{};
     p.B = B;
     p.T = T;
     p.N = T * 160;
@@ -345,10 +349,6 @@ int run_forward(fpc_wavenet* m, const float* feat, const int* periods, const flo
         fpc::set_error("fpc_wavenet: B = %d, T = %d make more than 2^31 workgroups; chunked passes are not built", B, T);
         return FPC_ERR_CAPACITY;
     }
-    FwdWorkspace w;
-    fwd_floats(m, B, T, &w, static_cast<float*>(workspace));
-    const int rc = run_condition(m, feat, periods, B, T, w.c.cfeat, 0, w.c, st);
-    if (rc != FPC_OK) return rc;
     p.R = c.residual_channels;
     p.G = c.gate_channels;
     p.S = c.skip_channels;
@@ -371,6 +371,20 @@ int run_forward(fpc_wavenet* m, const float* feat, const int* periods, const flo
     p.w_f2 = m->w_f2.as<float4>();
     p.b_f2[0] = m->b_f2[0];
     p.b_f2[1] = m->b_f2[1];
+    return FPC_OK;
+}
+
+// x != null: the input channels are built from x and the LPC taps into the workspace; else `inp` holds the caller's own
+int run_forward(fpc_wavenet* m, const float* feat, const int* periods, const float* lpc, const float* x, const float* inp, int B,
+                int T, float* stats, void* workspace, hipStream_t st) {
+    const int tn = pick_tn(m);
+    ForwardParams p{};
+    const int rc0 = forward_params(m, B, T, tn, p);
+    if (rc0 != FPC_OK) return rc0;
+    FwdWorkspace w;
+    fwd_floats(m, B, T, &w, static_cast<float*>(workspace));
+    const int rc = run_condition(m, feat, periods, B, T, w.c.cfeat, 0, w.c, st);
+    if (rc != FPC_OK) return rc;
     p.x = x;
     p.lpc = lpc;
     p.inp_out = w.inp;
@@ -380,6 +394,246 @@ int run_forward(fpc_wavenet* m, const float* feat, const int* periods, const flo
     p.stats = stats;
     if (x) k_wnf_inputs<<<(unsigned)std::min<long long>(((long long)B * p.N + 255) / 256, 1 << 20), 256, 0, st>>>(p);
     return tn == 64 ? launch_forward<64>(m, p, w, st) : tn == 32 ? launch_forward<32>(m, p, w, st) : launch_forward<16>(m, p, w, st);
+}
+
+// ---- the loss and the backward pass (wavenet_backward.h) ----
+
+constexpr int WG_SEGS = 32;  // position segments of a weight gradient at most
+constexpr int WG_CPS = 2;    // 16-position chunks per segment at least: short float32 chains, the segments add in float64
+
+size_t bwd_lds_bytes(const fpc_wavenet_config& c, int tn) {
+    return (size_t)(c.residual_channels + c.skip_channels + 2 * c.gate_channels) * tn * sizeof(float);
+}
+
+int pick_btn(const fpc_wavenet* m) {
+    if (m->btn) return m->btn;
+    return bwd_lds_bytes(m->c, 32) <= LDS_BYTES ? 32 : 16;  // 16 fits every model `validate` admits: 2048 rows x 16 = 128 KiB
+}
+
+struct BwdWorkspace {
+    Workspace c;
+    float *hs, *ts, *skip, *osave, *stats, *dstats, *dskip, *do1, *da, *dhp, *dh[2], *e0[2], *part;
+    double* lossb;
+};
+// the largest padded dW of the five weight-gradient products
+long long wg_part_floats(const fpc_wavenet* m) {
+    const fpc_wavenet_config& c = m->c;
+    const auto up64 = [](long long v) { return (v + 63) / 64 * 64; };
+    const long long R = c.residual_channels, G = c.gate_channels, S = c.skip_channels;
+    const long long M[5] = {2 * G, R + S, R, S, 16}, K[5] = {2 * R + m->coutp, G, c.inp_channels * FRONT, S, S};
+    long long mk = 0;
+    for (int i = 0; i < 5; ++i) mk = std::max(mk, up64(M[i]) * up64(K[i]));
+    return mk;
+}
+// B T [160 (cout + L R + L 2G + 4 S + 4 + 2G + 5 R) + 12 cout] + 2 B + WG_SEGS max M K
+long long bwd_floats(const fpc_wavenet* m, long long B, long long T, BwdWorkspace* w, float* base) {
+    const long long N = 160 * T, cf = B * m->c.cout_channels * N, fr = B * T * m->c.cout_channels, L = m->layers;
+    const long long h = B * m->c.residual_channels * N, sk = B * m->c.skip_channels * N, g2 = 2 * B * m->c.gate_channels * N;
+    const long long mk = wg_part_floats(m);
+    if (w) {
+        float* q = base;
+        const auto take = [&](long long n) {
+            float* r = q;
+            q += n;
+            return r;
+        };
+        w->c.cfeat = take(cf);
+        w->c.fa = take(fr);
+        w->c.fb = take(fr);
+        w->c.u1 = take(10 * fr);
+        w->c.ring = nullptr;
+        w->hs = take(L * h);
+        w->ts = take(L * g2);
+        w->skip = take(sk);
+        w->osave = take(sk);
+        w->dskip = take(sk);
+        w->do1 = take(sk);
+        w->stats = take(2 * B * N);
+        w->dstats = take(2 * B * N);
+        w->da = take(g2);
+        w->dhp = take(h);
+        w->dh[0] = take(h);
+        w->dh[1] = take(h);
+        w->e0[0] = take(h);
+        w->e0[1] = take(h);
+        w->part = take(WG_SEGS * mk);
+        w->lossb = reinterpret_cast<double*>(take(2 * B));  // an even offset: every count above is even
+    }
+    return cf + 12 * fr + L * h + L * g2 + 4 * sk + 4 * B * N + g2 + 5 * h + WG_SEGS * mk + 2 * B;
+}
+
+WgRows wg_rows(const float* src, long long bstride, int rows, int valid, int shift = 0) {
+    return WgRows{src, bstride, rows, valid, shift, 0, 1, WG_PLAIN, 0, nullptr};
+}
+
+// dW = sum_p A Bop^T over all B N positions, then the segments in order into the tensors `o` names
+int run_wgrad(WgradParams p, WgOut o, int B, int N, const BwdWorkspace& w, hipStream_t st) {
+    p.N = N;
+    p.chunks = B * (N / 16);
+    p.cps = std::max(WG_CPS, (p.chunks + WG_SEGS - 1) / WG_SEGS);
+    const int segs = (p.chunks + p.cps - 1) / p.cps;
+    p.mblocks = (p.a.total + 63) / 64;
+    p.kblocks = (p.bop.total + 63) / 64;
+    p.part = w.part;
+    o.segs = segs;
+    o.MP = p.mblocks * 64;
+    o.KP = p.kblocks * 64;
+    o.part = w.part;
+    k_wnb_wgrad<<<dim3((unsigned)(p.mblocks * p.kblocks), (unsigned)segs), 64, 0, st>>>(p);
+    k_wnb_reduce<<<(unsigned)(((long long)o.M * o.K + 255) / 256), 256, 0, st>>>(o);
+    k_wnb_rowsum<<<o.M, 256, 0, st>>>(p.a, o, B, N);
+    return FPC_OK;
+}
+
+template <int TN>
+int launch_backward(const fpc_wavenet* m, BackwardParams p, const BwdWorkspace& w, const float* inp, const fpc_wavenet_grads& g,
+                    hipStream_t st) {
+    const fpc_wavenet_config& c = m->c;
+    const int B = p.B, N = p.N, R = p.R, G = p.G, S = p.S, cout = p.cout, coutp = p.coutp, L = m->layers;
+    p.tiles = (N + TN - 1) / TN;
+    const unsigned grid = (unsigned)((long long)B * p.tiles);
+    const size_t lds_layer = bwd_lds_bytes(c, TN), lds_final = (size_t)S * TN * sizeof(float);
+    FPC_HIP(hipFuncSetAttribute((const void*)k_wnb_layer<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer));
+    FPC_HIP(hipFuncSetAttribute((const void*)k_wnb_final<TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_final));
+    const long long hsz = (long long)B * R * N, gsz = 2ll * B * G * N;
+
+    k_wnb_loss<<<B, 256, 0, st>>>(p);
+    k_wnb_loss_sum<<<1, 1, 0, st>>>(p);
+    k_wnb_final<TN><<<grid, THREADS, lds_final, st>>>(p);
+    {   // final_conv.3: dstats . o^T;  final_conv.1: do1 . relu(skip + b_skip)^T
+        WgradParams q{};
+        q.a.g[0] = wg_rows(w.dstats, 2ll * N, 16, 2);
+        q.a.total = 16;
+        q.bop.g[0] = wg_rows(w.osave, (long long)S * N, S, S);
+        q.bop.total = S;
+        WgOut o{};
+        o.M = 2, o.K = S, o.msplit = 2, o.kend[0] = o.kvalid[0] = S, o.rs[0] = S, o.cs[0] = 1;
+        o.w[0][0] = g.final2_w, o.bias[0][0] = g.final2_b;
+        run_wgrad(q, o, B, N, w, st);
+        q.a.g[0] = wg_rows(w.do1, (long long)S * N, S, S);
+        q.a.total = S;
+        q.bop.g[0] = wg_rows(w.skip, (long long)S * N, S, S);
+        q.bop.g[0].mode = WG_RELU_BIAS;
+        q.bop.g[0].bias = m->b_skip.as<float>();
+        o.M = S, o.msplit = S;
+        o.w[0][0] = g.final1_w, o.bias[0][0] = g.final1_b;
+        run_wgrad(q, o, B, N, w, st);
+    }
+    const int K1 = 2 * R + coutp;
+    for (int n = L - 1; n >= 0; --n) {
+        const int d = 1 << (n % c.num_layers), k = (L - 1 - n) & 1;  // this launch writes dh[k], e0[k] and reads [k ^ 1]
+        p.w2t = m->w2t.as<float4>() + (long long)n * (G / 16) * p.K2q * 64;
+        p.w1t = m->w1t.as<float4>() + (long long)n * (K1 / 16) * p.K1q * 64;
+        p.ts = w.ts + n * gsz;
+        p.last = p.first = n == L - 1;
+        p.dil_next = n + 1 < L ? 1 << ((n + 1) % c.num_layers) : 0;
+        p.dh_in = w.dh[k ^ 1];
+        p.e0_in = w.e0[k ^ 1];
+        p.dh_out = w.dh[k];
+        p.e0_out = w.e0[k];
+        k_wnb_layer<TN><<<grid, THREADS, lds_layer, st>>>(p);
+        const float* hn = w.hs + n * hsz;
+        WgradParams q{};  // dW1 = da . [h(p - d); h(p); c(p)]^T
+        q.a.g[0] = wg_rows(w.da, 2ll * G * N, 2 * G, 2 * G);
+        q.a.total = 2 * G;
+        q.bop.g[0] = wg_rows(hn, (long long)R * N, R, R, d);
+        q.bop.g[1] = wg_rows(hn, (long long)R * N, R, R);
+        q.bop.g[2] = wg_rows(w.c.cfeat, (long long)cout * N, coutp, cout);
+        q.bop.total = K1;
+        WgOut o{};
+        o.M = 2 * G, o.K = K1, o.msplit = G;
+        o.kend[0] = R, o.kend[1] = 2 * R, o.kend[2] = K1;
+        o.kvalid[0] = o.kvalid[1] = R, o.kvalid[2] = cout;
+        o.rs[0] = o.rs[1] = 2 * R, o.cs[0] = o.cs[1] = 2, o.rs[2] = cout, o.cs[2] = 1;
+        const long long wo = (long long)n * G * R * 2, co = (long long)n * G * cout, bo = (long long)n * G;
+        o.w[0][0] = g.filter_w + wo, o.w[0][1] = g.filter_w + wo + 1, o.w[0][2] = g.filter_c_w + co;
+        o.w[1][0] = g.gate_w + wo, o.w[1][1] = g.gate_w + wo + 1, o.w[1][2] = g.gate_c_w + co;
+        o.bias[0][0] = g.filter_b + bo, o.bias[0][1] = g.filter_c_b + bo;
+        o.bias[1][0] = g.gate_b + bo, o.bias[1][1] = g.gate_c_b + bo;
+        run_wgrad(q, o, B, N, w, st);
+        q = WgradParams{};  // dW2 = [sqrt(1/2) dh'; dskip] . (t s)^T
+        q.a.g[0] = wg_rows(w.dhp, (long long)R * N, R, R);
+        q.a.g[1] = wg_rows(w.dskip, (long long)S * N, S, S);
+        q.a.total = R + S;
+        q.bop.g[0] = wg_rows(p.ts, 2ll * G * N, G, G);
+        q.bop.g[0].mode = WG_PRODUCT;
+        q.bop.g[0].aux_off = (long long)G * N;
+        q.bop.total = G;
+        o = WgOut{};
+        o.M = R + S, o.K = G, o.msplit = R, o.kend[0] = o.kvalid[0] = G, o.rs[0] = G, o.cs[0] = 1;
+        o.w[0][0] = g.res_w + (long long)n * R * G, o.w[1][0] = g.skip_w + (long long)n * S * G;
+        o.bias[0][0] = g.res_b + (long long)n * R, o.bias[1][0] = g.skip_b + (long long)n * S;
+        run_wgrad(q, o, B, N, w, st);
+    }
+    // the front convolution: the first block wrote dh[(L - 1) & 1]; dpre0 takes dhp's place
+    p.dh_in = w.dh[(L - 1) & 1];
+    p.e0_in = w.e0[(L - 1) & 1];
+    p.dil_next = 1;
+    p.h0 = w.hs;
+    p.dpre0 = w.dhp;
+    k_wnb_front<<<(unsigned)std::min<long long>((hsz + 255) / 256, 1 << 20), 256, 0, st>>>(p);
+    WgradParams q{};
+    q.a.g[0] = wg_rows(w.dhp, (long long)R * N, R, R);
+    q.a.total = R;
+    q.bop.g[0] = WgRows{inp, (long long)c.inp_channels * N, c.inp_channels * FRONT, c.inp_channels * FRONT, FRONT - 1, -1, FRONT,
+                        WG_PLAIN, 0, nullptr};
+    q.bop.total = c.inp_channels * FRONT;
+    WgOut o{};
+    o.M = R, o.K = c.inp_channels * FRONT, o.msplit = R, o.kend[0] = o.kvalid[0] = o.K, o.rs[0] = o.K, o.cs[0] = 1;
+    o.w[0][0] = g.front_w, o.bias[0][0] = g.front_b;
+    run_wgrad(q, o, B, N, w, st);
+    FPC_HIP(hipGetLastError());
+    return FPC_OK;
+}
+
+int run_loss_backward(fpc_wavenet* m, const float* feat, const int* periods, const float* inp, const float* target, int n_valid,
+                      int B, int T, float* loss, const fpc_wavenet_grads& g, void* workspace, hipStream_t st) {
+    const int tn = pick_tn(m), btn = pick_btn(m);
+    ForwardParams f{};
+    const int rc0 = forward_params(m, B, T, std::min(tn, 16), f);  // 16: the bound on the grid covers every instance
+    if (rc0 != FPC_OK) return rc0;
+    f.tiles = (f.N + tn - 1) / tn;
+    BwdWorkspace w;
+    bwd_floats(m, B, T, &w, static_cast<float*>(workspace));
+    const int rc = run_condition(m, feat, periods, B, T, w.c.cfeat, 0, w.c, st);
+    if (rc != FPC_OK) return rc;
+    FwdWorkspace fw{};
+    fw.c = w.c;
+    fw.skip = w.skip;
+    f.inp_in = inp;
+    f.cfeat = w.c.cfeat;
+    f.skip = w.skip;
+    f.stats = w.stats;
+    f.osave = w.osave;
+    const int rc1 = tn == 64   ? launch_forward<64, true>(m, f, fw, st, w.hs, w.ts)
+                    : tn == 32 ? launch_forward<32, true>(m, f, fw, st, w.hs, w.ts)
+                               : launch_forward<16, true>(m, f, fw, st, w.hs, w.ts);
+    if (rc1 != FPC_OK) return rc1;
+    BackwardParams p{};
+    p.B = B;
+    p.N = f.N;
+    p.R = f.R, p.G = f.G, p.S = f.S, p.cout = f.cout, p.coutp = f.coutp;
+    p.K2q = (p.R + p.S) / 16;
+    p.K1q = 2 * p.G / 16;
+    p.Sq = p.S / 16;
+    p.n_valid = n_valid;
+    p.inv_m = 1.0 / ((double)B * n_valid);
+    p.stats = w.stats;
+    p.target = target;
+    p.dstats = w.dstats;
+    p.lossb = w.lossb;
+    p.loss = loss;
+    p.f2 = m->f2.as<float>();
+    p.w_f1t = m->w_f1t.as<float4>();
+    p.osave = w.osave;
+    p.skip = w.skip;
+    p.b_skip = m->b_skip.as<float>();
+    p.do1 = w.do1;
+    p.dskip = w.dskip;
+    p.dhp = w.dhp;
+    p.da = w.da;
+    p.dc = g.cfeat;
+    return btn == 32 ? launch_backward<32>(m, p, w, inp, g, st) : launch_backward<16>(m, p, w, inp, g, st);
 }
 
 }  // namespace
@@ -501,6 +755,32 @@ extern "C" int fpc_wavenet_create(const fpc_wavenet_config* cfg, const fpc_waven
     FPC_HIP(m->w_f2.upload(v));
     m->b_f2[0] = w->final2_b[0];
     m->b_f2[1] = w->final2_b[1];
+
+    // the backward pass's A operands (wavenet_backward.h): the same matrices transposed, in the same fragment order
+    const auto w1_at = [&](int n, int row, int k) {  // [2G x K1] of layer n as packed above
+        const int fg = row >= G, g = row - fg * G;
+        const float* cw = (fg ? w->gate_w : w->filter_w) + (size_t)n * G * R * 2;
+        const float* cc = (fg ? w->gate_c_w : w->filter_c_w) + (size_t)n * G * cout;
+        if (k < R) return cw[((size_t)g * R + k) * 2];
+        if (k < 2 * R) return cw[((size_t)g * R + (k - R)) * 2 + 1];
+        return k - 2 * R < cout ? cc[(size_t)g * cout + (k - 2 * R)] : 0.0f;
+    };
+    v.clear();
+    for (int n = 0; n < L; ++n)
+        for (int t = 0; t < K1 / 16; ++t) pack_tile(v, 2 * G / 16, [&](int r, int k) { return w1_at(n, k, t * 16 + r); });
+    FPC_HIP(m->w1t.upload(v));
+    v.clear();
+    for (int n = 0; n < L; ++n)
+        for (int t = 0; t < G / 16; ++t)
+            pack_tile(v, (R + S) / 16, [&](int r, int k) {
+                const size_t g = t * 16 + r;
+                return k < R ? w->res_w[((size_t)n * R + k) * G + g] : w->skip_w[((size_t)n * S + k - R) * G + g];
+            });
+    FPC_HIP(m->w2t.upload(v));
+    v.clear();
+    for (int t = 0; t < S / 16; ++t) pack_tile(v, S / 16, [&](int r, int k) { return w->final1_w[(size_t)k * S + t * 16 + r]; });
+    FPC_HIP(m->w_f1t.upload(v));
+    FPC_HIP(up(m->f2, w->final2_w, (size_t)2 * S));
     FPC_HIP(m->dil_d.upload(dil));
     FPC_HIP(m->off_d.upload(off));
     FPC_HIP(hipEventCreate(&m->ev0));
@@ -597,6 +877,54 @@ extern "C" int fpc_wavenet_forward_input(fpc_wavenet* m, const float* feat_dev, 
     FPC_REQUIRE(feat_dev && periods_dev && inp_dev && stats_dev, "fpc_wavenet_forward_input: null pointer");
     return run_forward(m, feat_dev, periods_dev, nullptr, nullptr, inp_dev, B, T, stats_dev, workspace_dev,
                        static_cast<hipStream_t>(s));
+}
+
+extern "C" long long fpc_wavenet_backward_workspace_bytes(const fpc_wavenet* m, int B, int T) {
+    if (!m || B < 1 || T < 1) {
+        fpc::set_error("fpc_wavenet_backward_workspace_bytes: null handle or B, T < 1");
+        return FPC_ERR_INVALID;
+    }
+    return 4 * bwd_floats(m, B, T, nullptr, nullptr);
+}
+
+extern "C" long long fpc_wavenet_backward_stats_offset(const fpc_wavenet* m, int B, int T) {
+    if (!m || B < 1 || T < 1) {
+        fpc::set_error("fpc_wavenet_backward_stats_offset: null handle or B, T < 1");
+        return FPC_ERR_INVALID;
+    }
+    BwdWorkspace w;
+    bwd_floats(m, B, T, &w, nullptr);
+    return (long long)reinterpret_cast<uintptr_t>(w.stats);
+}
+
+extern "C" int fpc_wavenet_set_backward_tile(fpc_wavenet* m, int tn) {
+    FPC_REQUIRE(m != nullptr, "fpc_wavenet_set_backward_tile: null handle");
+    FPC_REQUIRE(tn == 0 || tn == 16 || tn == 32, "fpc_wavenet_set_backward_tile: tn = %d, not 0, 16 or 32", tn);
+    if (tn && bwd_lds_bytes(m->c, tn) > LDS_BYTES) {
+        fpc::set_error("fpc_wavenet_set_backward_tile: tn = %d needs %zu bytes of LDS for this model, the device has %zu", tn,
+                       bwd_lds_bytes(m->c, tn), LDS_BYTES);
+        return FPC_ERR_CAPACITY;
+    }
+    m->btn = tn;
+    return FPC_OK;
+}
+
+extern "C" int fpc_wavenet_backward_tile(const fpc_wavenet* m) { return m ? pick_btn(m) : (int)FPC_ERR_INVALID; }
+
+extern "C" int fpc_wavenet_loss_backward(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* inp_dev,
+                                         const float* target_dev, int n_valid, int B, int T, float* loss_dev,
+                                         const fpc_wavenet_grads* grads, void* workspace_dev, fpc_stream s) {
+    FPC_REQUIRE(m != nullptr, "fpc_wavenet_loss_backward: null handle");
+    FPC_REQUIRE(feat_dev && periods_dev && inp_dev && target_dev && loss_dev && grads, "fpc_wavenet_loss_backward: null pointer");
+    FPC_REQUIRE(n_valid >= 1 && n_valid <= 160ll * T, "fpc_wavenet_loss_backward: n_valid = %d outside [1, 160 T], T = %d", n_valid, T);
+    const int rc = check_call(m, B, T, workspace_dev);
+    if (rc != FPC_OK) return rc;
+    float* const* gp = reinterpret_cast<float* const*>(grads);
+    for (size_t i = 0; i < sizeof(*grads) / sizeof(float*); ++i)
+        FPC_REQUIRE(gp[i] != nullptr, "fpc_wavenet_loss_backward: gradient pointer %zu is null", i);
+    FPC_REQUIRE(((uintptr_t)inp_dev & 15) == 0, "fpc_wavenet_loss_backward: inp must be 16-byte aligned");
+    return run_loss_backward(m, feat_dev, periods_dev, inp_dev, target_dev, n_valid, B, T, loss_dev, *grads, workspace_dev,
+                             static_cast<hipStream_t>(s));
 }
 
 extern "C" float fpc_wavenet_last_decode_ms(fpc_wavenet* m) {

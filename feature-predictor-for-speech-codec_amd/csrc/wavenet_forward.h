@@ -66,6 +66,8 @@ struct ForwardParams {
     float* hout;                      // [B][R][N]
     float* skip;                      // [B][S][N]
     float* stats;                     // [B][N][2]
+    float* ts;                        // [B][2G][N] of THIS layer: t = tanh(a_f), s = sigmoid(a_g)   (SAVE instances only)
+    float* osave;                     // [B][S][N]: the last stage's hidden ReLU output              (SAVE instances only)
 };
 
 // The net's input at position p, as k_wn_decode's stage 0 and tail build it: u = x(p-1); with inp = 3 also
@@ -166,8 +168,9 @@ __device__ __forceinline__ void stage_rows(float* dst, int ps, int row0, int nro
     }
 }
 
-// One residual block (modules.py:62-77) for one utterance x TN positions.
-template <int TN>
+// One residual block (modules.py:62-77) for one utterance x TN positions.  SAVE (wavenet_backward.h): t and s also go to
+// p.ts for the backward pass; the arithmetic is the same, so the stats are the same bits.
+template <int TN, bool SAVE = false>
 __global__ __launch_bounds__(THREADS) void k_wnf_layer(const ForwardParams p) {
     constexpr int NT = TN / 16;
     extern __shared__ float lds[];
@@ -202,8 +205,20 @@ __global__ __launch_bounds__(THREADS) void k_wnf_layer(const ForwardParams p) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                Z[nt * psZ + (t * 16 + 4 * kl + r) * 16 + j] = tanh_e(acc[0][nt][r] + bf[r]) * sigmoid_e(acc[1][nt][r] + bg[r]);
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (SAVE) {
+                    const float tv = tanh_e(acc[0][nt][r] + bf[r]), sv = sigmoid_e(acc[1][nt][r] + bg[r]);
+                    const int g = t * 16 + 4 * kl + r;
+                    const long long pos = p0 + nt * 16 + j;
+                    Z[nt * psZ + g * 16 + j] = tv * sv;
+                    if (pos < N) {
+                        p.ts[(b * 2 * G + g) * N + pos] = tv;
+                        p.ts[(b * 2 * G + G + g) * N + pos] = sv;
+                    }
+                } else {
+                    Z[nt * psZ + (t * 16 + 4 * kl + r) * 16 + j] = tanh_e(acc[0][nt][r] + bf[r]) * sigmoid_e(acc[1][nt][r] + bg[r]);
+                }
+            }
     }
     __syncthreads();
 
@@ -245,7 +260,8 @@ __global__ __launch_bounds__(THREADS) void k_wnf_layer(const ForwardParams p) {
 }
 
 // ReLU, 1x1 S->S, ReLU, 1x1 S->2 (wavenet.py:50-56).  LDS: Z [TN/16][S][16] relu(skip + b_skip), O [TN/16][S][16].
-template <int TN>
+// SAVE: O also goes to p.osave.
+template <int TN, bool SAVE = false>
 __global__ __launch_bounds__(THREADS) void k_wnf_final(const ForwardParams p) {
     constexpr int NT = TN / 16;
     extern __shared__ float lds[];
@@ -274,7 +290,14 @@ __global__ __launch_bounds__(THREADS) void k_wnf_final(const ForwardParams p) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) O[nt * psS + (t * 16 + 4 * kl + r) * 16 + j] = fmaxf(acc[0][nt][r] + bias[r], 0.0f);
+            for (int r = 0; r < 4; ++r) {
+                const float o = fmaxf(acc[0][nt][r] + bias[r], 0.0f);
+                O[nt * psS + (t * 16 + 4 * kl + r) * 16 + j] = o;
+                if constexpr (SAVE) {
+                    const long long pos = p0 + nt * 16 + j;
+                    if (pos < N) p.osave[(b * S + t * 16 + 4 * kl + r) * N + pos] = o;
+                }
+            }
     }
     __syncthreads();
     for (int nt = wave; nt < NT; nt += WAVES) {  // rows 0 and 1 (mean, log_std) of N tile nt land in lanes 0..15

@@ -1,6 +1,7 @@
 """The reference's own vocoder: the Gaussian-output WaveNet of src/models/wavenet.py, decoded by k_wn_decode
 (csrc/wavenet_decode.h) for a whole batch of utterances, and evaluated teacher-forced over all positions at once by the k_wnf_*
-kernels (csrc/wavenet_forward.h).  `Wavenet` takes the reference's constructor arguments and its
+kernels (csrc/wavenet_forward.h); `loss_backward` adds the Gaussian loss and the backward pass of the sample-level network
+(k_wnb_*, csrc/wavenet_backward.h).  `Wavenet` takes the reference's constructor arguments and its
 state_dict, key for key; `forward`, `generate_lpc`, `upsample` and `forward_stats` take the reference's tensor layouts."""
 import ctypes as C
 
@@ -10,6 +11,13 @@ import torch
 from . import _lib
 
 FRAME = 160
+
+
+_NORMED = ((".weight_g", ".weight_v"), (".parametrizations.weight.original0", ".parametrizations.weight.original1"))
+# ABI name of a sample-level weight -> the reference's module name ({} = "res_blocks.n.")
+_MODULES = {"front": "front_conv.0.conv", "filter": "{}filter_conv.conv", "gate": "{}gate_conv.conv",
+            "filter_c": "{}filter_conv_c", "gate_c": "{}gate_conv_c", "res": "{}res_conv", "skip": "{}skip_conv",
+            "final1": "final_conv.1.conv", "final2": "final_conv.3.conv"}
 
 
 def _folded(sd, name):
@@ -38,6 +46,8 @@ class Wavenet:
         self.w = None
         self._ws = None
         self._fws = None
+        self._bws = None
+        self._gv = {}  # module name -> (key of g, key of v, g, v) on the device, where the state_dict was weight-normed
         self.tn = tn
         self._create(None)
         self.nfeat = cin_channels - 64
@@ -99,6 +109,13 @@ class Wavenet:
                 raise ValueError(f"{k}: shape {tuple(w[k].shape)} != {s}")
         self.w = {k: np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32) for k, v in w.items()}
         self._create(_lib.WavenetWeights(*[self.w[k].ctypes.data for k in _lib.WAVENET_KEYS]))
+        self._gv = {}
+        for mod in _MODULES.values():
+            for name in ([mod.format(f"res_blocks.{n}.") for n in range(L)] if "{}" in mod else [mod]):
+                for kg, kv in _NORMED:
+                    if name + kg in sd:
+                        self._gv[name] = (name + kg, name + kv, torch.as_tensor(sd[name + kg]).float().cuda(),
+                                          torch.as_tensor(sd[name + kv]).float().cuda())
         return self
 
     # ---- calls ----
@@ -194,6 +211,71 @@ class Wavenet:
         return st.transpose(1, 2)
 
     __call__ = forward
+
+    def backward_workspace_bytes(self, B, T):
+        return int(_lib.lib().fpc_wavenet_backward_workspace_bytes(self.handle, B, T))
+
+    def set_backward_tile(self, tn):
+        """positions per workgroup of the backward's data-gradient kernels: 16, 32, 0 = automatic"""
+        _lib.check(_lib.lib().fpc_wavenet_set_backward_tile(self.handle, tn), "fpc_wavenet_set_backward_tile")
+
+    def backward_tile(self):
+        return int(_lib.lib().fpc_wavenet_backward_tile(self.handle))
+
+    def loss_backward(self, x, periods, c, target, n_valid=None, return_stats=False):
+        """train.py:137-140 without the optimiser: forward(x, periods, c), gaussianloss(dist[:, :, :-1], target[:, :, 1:]) and
+        its backward through the sample-level network.  x (B,inp_channels,160L), target (B,1,160L) or (B,160L) (the reference's
+        exc); n_valid: positions of every utterance that count (default all 160L - 1).  -> (loss, grads): loss a 0-d tensor,
+        grads keyed by the reference's state_dict names (weight_g / weight_v where the loaded state_dict had them, by
+        weight_norm's closed form; else weight) plus "cfeat" (B,cout,160L), the gradient of upsample(c, periods).
+        return_stats: also the (B,2,160L) stats of this pass, forward()'s bits."""
+        f, p, _, B, T = self._inputs(c, periods, None)
+        N, cfg, L = T * FRAME, self.cfg, self.layers
+        xs = torch.as_tensor(x).to("cuda", torch.float32).contiguous().clone()
+        if tuple(xs.shape) != (B, cfg.inp_channels, N):
+            raise ValueError(f"x has shape {tuple(xs.shape)}, not {(B, cfg.inp_channels, N)}")
+        y = torch.as_tensor(target).to("cuda", torch.float32).reshape(B, N)
+        y = torch.cat((y[:, 1:], y.new_zeros(B, 1)), 1).contiguous()  # position p is scored against target[p + 1]
+        n_valid = N - 1 if n_valid is None else int(n_valid)
+        if not 1 <= n_valid <= N - 1:
+            raise ValueError(f"n_valid = {n_valid} outside [1, {N - 1}]")
+        R, G, S, co = cfg.residual_channels, cfg.gate_channels, cfg.skip_channels, cfg.cout_channels
+        shapes = {"front_w": (R, cfg.inp_channels, 32), "front_b": (R,), "filter_w": (L, G, R, 2), "gate_w": (L, G, R, 2),
+                  "filter_c_w": (L, G, co, 1), "gate_c_w": (L, G, co, 1), "res_w": (L, R, G, 1), "skip_w": (L, S, G, 1),
+                  "res_b": (L, R), "skip_b": (L, S), "final1_w": (S, S, 1), "final1_b": (S,), "final2_w": (2, S, 1),
+                  "final2_b": (2,), "cfeat": (B, co, N)}
+        g = {k: torch.empty(shapes.get(k, (L, G)), device="cuda") for k in _lib.WAVENET_GRAD_KEYS}
+        loss = torch.empty((), device="cuda")
+        need = self.backward_workspace_bytes(B, T)
+        if need < 0:
+            _lib.check(need, "fpc_wavenet_backward_workspace_bytes")
+        if self._bws is None or self._bws.numel() < need:
+            self._bws = None
+            self._bws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        gs = _lib.WavenetGrads(*[g[k].data_ptr() for k in _lib.WAVENET_GRAD_KEYS])
+        _lib.check(_lib.lib().fpc_wavenet_loss_backward(self.handle, f.data_ptr(), p.data_ptr(), xs.data_ptr(), y.data_ptr(),
+                                                        n_valid, B, T, loss.data_ptr(), C.byref(gs), self._bws.data_ptr(),
+                                                        _lib.stream_ptr()), "fpc_wavenet_loss_backward")
+        out = {"cfeat": g["cfeat"]}
+        for key, mod in _MODULES.items():
+            for n in (range(L) if "{}" in mod else [None]):
+                name = mod.format(f"res_blocks.{n}.")
+                dw, db = (g[key + "_w"], g[key + "_b"]) if n is None else (g[key + "_w"][n], g[key + "_b"][n])
+                out[name + ".bias"] = db
+                if name not in self._gv:
+                    out[name + ".weight"] = dw
+                    continue
+                kg, kv, gg, v = self._gv[name]  # w = g v / |v|, the norm over all dimensions but 0
+                dims = tuple(range(1, v.dim()))
+                norm = v.pow(2).sum(dims, keepdim=True).sqrt()
+                dot = (dw * v).sum(dims, keepdim=True)
+                out[kg] = dot / norm
+                out[kv] = (gg / norm) * (dw - v * dot / norm.pow(2))
+        if return_stats:
+            off = int(_lib.lib().fpc_wavenet_backward_stats_offset(self.handle, B, T))
+            st = self._bws[off:off + 8 * B * N].view(torch.float32).reshape(B, N, 2).transpose(1, 2).clone()
+            return loss, out, st
+        return loss, out
 
     def forward_stats(self, x, feat, periods, lpc, time_parallel=False):
         """teacher-forced: x (B,1,160L) or (B,160L) -> (B,2,160L), (mean, log_std) of every sample given the ones before

@@ -37,7 +37,9 @@ extern "C" {
  *    fpc_wavenet_create / _destroy, fpc_wavenet_workspace_bytes, fpc_wavenet_synthesize, fpc_wavenet_forward,
  *    fpc_wavenet_condition, fpc_wavenet_last_decode_ms;
  *    fpc_wavenet_forward_parallel, fpc_wavenet_forward_input, fpc_wavenet_forward_workspace_bytes,
- *    fpc_wavenet_set_forward_tile, fpc_wavenet_forward_tile. */
+ *    fpc_wavenet_set_forward_tile, fpc_wavenet_forward_tile;
+ *    fpc_wavenet_loss_backward, fpc_wavenet_backward_workspace_bytes, fpc_wavenet_backward_stats_offset,
+ *    fpc_wavenet_set_backward_tile, fpc_wavenet_backward_tile. */
 #define FPC_ABI_VERSION 4
 #define FPC_API __attribute__((visibility("default")))
 
@@ -476,6 +478,64 @@ FPC_API long long fpc_wavenet_forward_workspace_bytes(const fpc_wavenet* m, int 
  * shape, where two such workgroups share a compute unit), else 16.  The result does not depend on it.  FPC_ERR_CAPACITY if the model's panels do not fit at tn.  _forward_tile: the width in effect. */
 FPC_API int fpc_wavenet_set_forward_tile(fpc_wavenet* m, int tn);
 FPC_API int fpc_wavenet_forward_tile(const fpc_wavenet* m);
+
+/* DEVICE pointers that receive the gradients of fpc_wavenet_loss_backward: the sample-level members of fpc_wavenet_weights in
+ * the same (PyTorch) layouts, with respect to the folded weights, plus the gradient of the upsampled conditioning.  The two
+ * conditioning biases of a block receive the same sum as its filter / gate bias, every skip bias the same sum, and the last
+ * block's res_w / res_b zeros (its residual output is never read). */
+typedef struct {
+    float* front_w;    /* [R,inp,32] */
+    float* front_b;    /* [R] */
+    float* filter_w;   /* [layers,G,R,2] */
+    float* filter_b;   /* [layers,G] */
+    float* gate_w;     /* [layers,G,R,2] */
+    float* gate_b;     /* [layers,G] */
+    float* filter_c_w; /* [layers,G,cout] */
+    float* filter_c_b; /* [layers,G] */
+    float* gate_c_w;   /* [layers,G,cout] */
+    float* gate_c_b;   /* [layers,G] */
+    float* res_w;      /* [layers,R,G] */
+    float* res_b;      /* [layers,R] */
+    float* skip_w;     /* [layers,S,G] */
+    float* skip_b;     /* [layers,S] */
+    float* final1_w;   /* [S,S] */
+    float* final1_b;   /* [S] */
+    float* final2_w;   /* [2,S] */
+    float* final2_b;   /* [2] */
+    float* cfeat;      /* [B,cout,160T] */
+} fpc_wavenet_grads;
+
+/* One training pass of the sample-level network (src/train.py:137-140 without the optimiser), on the caller's stream:
+ * Wavenet.forward on inp [B,inp_channels,160T] (as fpc_wavenet_forward_input; 16-byte aligned), saving what the backward
+ * needs; the Gaussian loss of src/loss.py:6-21 against target [B,160T] over the first n_valid positions of every utterance,
+ *   loss = mean of 0.5 (log 2 pi + 2 ls + (target - mean)^2 exp(-2 ls)),  ls = max(log_std, -9)
+ * (train.py:139 is n_valid = 160T - 1 with target[p] = exc[p + 1]); and the backward through the last stage, every residual
+ * block and the front convolution (csrc/wavenet_backward.h).  loss [1] float32 on the device.  The conditioning network's own
+ * backward, the optimiser, clipping and repacking of updated weights are not built: the caller receives grads->cfeat, and
+ * fpc_wavenet_create on the updated weights remains the route.  The loss and every gradient are the same bits on every run.
+ * FPC_ERR_INVALID: a null handle or pointer, n_valid outside [1, 160T]. */
+FPC_API int fpc_wavenet_loss_backward(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, const float* inp_dev,
+                              const float* target_dev, int n_valid, int B, int T, float* loss_dev,
+                              const fpc_wavenet_grads* grads, void* workspace_dev, fpc_stream s);
+
+/* Bytes of device workspace of fpc_wavenet_loss_backward for (B,T), N = 160T, L = num_blocks * num_layers (a pure function,
+ * serves a shape-only handle):
+ *   4 * ( B*N*(cout + L*R + L*2G + 4*S + 4 + 2G + 5*R) + 12*B*T*cout + 2*B + 32*MK )
+ * the conditioning and its intermediates; per block its input h and t, s; the skip sum, the last stage's hidden output and
+ * their two gradients; stats and their gradient; one block's gate gradients; five R-row gradient buffers; the utterances'
+ * loss sums; and the 32 position segments of the largest weight gradient, MK = max over the five products of
+ * ceil64(M)*ceil64(K).  Linear in B*T*L but for the last term, which depends on the shape alone.  At the
+ * configured shape (R/G/S 128/256/128, cout 128, 2 x 10 layers) and 16 x 10 frames: 1.52 GB.  < 0: a negative fpc_status. */
+FPC_API long long fpc_wavenet_backward_workspace_bytes(const fpc_wavenet* m, int B, int T);
+
+/* Byte offset, inside that workspace, of the stats [B,160T,2] the last fpc_wavenet_loss_backward computed: the same bits as
+ * fpc_wavenet_forward_input's. */
+FPC_API long long fpc_wavenet_backward_stats_offset(const fpc_wavenet* m, int B, int T);
+
+/* Positions per workgroup of k_wnb_final / k_wnb_layer: 16, 32, or 0 = automatic (32 where (R + S + 2G) * 32 floats fit the
+ * LDS, else 16).  FPC_ERR_CAPACITY if the panels do not fit at tn.  _backward_tile: the width in effect. */
+FPC_API int fpc_wavenet_set_backward_tile(fpc_wavenet* m, int tn);
+FPC_API int fpc_wavenet_backward_tile(const fpc_wavenet* m);
 
 /* Wavenet.upsample (wavenet.py:93-115): cfeat [B,cout,160T] */
 FPC_API int fpc_wavenet_condition(fpc_wavenet* m, const float* feat_dev, const int32_t* periods_dev, int B, int T,

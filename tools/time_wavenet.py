@@ -11,6 +11,11 @@ k_wnf_* pass with TN = 32 and 64, T = 10 and 300, B = 16 and 256, device events 
 
     python tools/time_wavenet.py --forward [--out profiles/wavenet_forward.txt] [--reps 3]
 
+--backward times Wavenet.loss_backward (forward + Gaussian loss + backward, k_wnb_*) beside forward() of the same tree, for each
+backward tile width, at B = 16 and 64, T = 10, and dense float32 PyTorch autograd of the plain network at 16 x 10.
+
+    python tools/time_wavenet.py --backward [--out profiles/wavenet_backward.txt] [--reps 5]
+
 Operations and bytes are computed from the shapes here; the peak is the 157.3 TFLOP/s f32 MFMA figure DESIGN.md quotes."""
 import argparse
 import os
@@ -143,20 +148,89 @@ def forward_leg(a, mac):
     return lines
 
 
+def torch_step(sd, inp, cf, y):
+    """dense float32 autograd of the plain network on the GPU: loss and gradients of every sample-level weight and of cf"""
+    w = {k: v.cuda().requires_grad_() for k, v in sd.items() if k.startswith(("front_conv", "res_blocks", "final_conv"))}
+    fold = lambda k: torch._weight_norm(w[k + ".weight_v"], w[k + ".weight_g"], 0)
+    cf = cf.detach().requires_grad_()
+
+    def step():
+        h = F.relu(F.conv1d(F.pad(inp, (31, 0)), fold("front_conv.0.conv"), w["front_conv.0.conv.bias"]))
+        skip = 0
+        for n in range(NB * NL):
+            p, d = f"res_blocks.{n}.", 2 ** (n % NL)
+            conv = lambda k: (F.conv1d(F.pad(h, (d, 0)), fold(p + k + ".conv"), w[p + k + ".conv.bias"], dilation=d)
+                              + F.conv1d(cf, fold(p + k + "_c"), w[p + k + "_c.bias"]))
+            z = torch.tanh(conv("filter_conv")) * torch.sigmoid(conv("gate_conv"))
+            skip = skip + F.conv1d(z, fold(p + "skip_conv"), w[p + "skip_conv.bias"])
+            h = (h + F.conv1d(z, fold(p + "res_conv"), w[p + "res_conv.bias"])) * 0.5 ** 0.5
+        st = F.conv1d(F.relu(F.conv1d(F.relu(skip), fold("final_conv.1.conv"), w["final_conv.1.conv.bias"])),
+                      fold("final_conv.3.conv"), w["final_conv.3.conv.bias"])
+        mean, ls = st[:, 0, :-1], st[:, 1, :-1].clamp(min=-9)
+        loss = (0.5 * (1.8378770664093453 + 2 * ls + (y[:, 1:] - mean) ** 2 * torch.exp(-2 * ls))).mean()
+        return torch.autograd.grad(loss, [v for k, v in w.items() if "res_blocks.%d.res_conv" % (NB * NL - 1) not in k] + [cf])[0]
+    return step
+
+
+def backward_leg(a, mac):
+    sd = state_dict()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    m = model(sd, 0)
+    lines = [f"Wavenet.loss_backward on {torch.cuda.get_device_name(0)} ({cus} CUs), R/G/S {R}/{G}/{S}, cout {CO}, {NB} x {NL} layers, "
+             f"inp_channels 1, T = 10; {a.reps} timed calls after two warm-ups, device events around the whole call",
+             f"MAC per position and utterance: forward {mac}, loss_backward counted as 3 x that; forward tile {m.forward_tile()}",
+             "  path            B   positions   ms (min / median / max)    TFLOP/s  of f32 MFMA peak   vs forward()"]
+
+    def timed(fn):
+        ms = []
+        for r in range(a.reps + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return min(ms[2:]), float(np.median(ms[2:])), max(ms[2:])
+
+    T = 10
+    for B in (16, 64):
+        g = torch.Generator().manual_seed(B)
+        feat, per = torch.randn(B, NFEAT, T, generator=g).cuda(), torch.randint(0, 256, (B, T, 1), generator=g).cuda()
+        x, y = (0.3 * torch.randn(B, 1, 160 * T, generator=g)).cuda(), (0.3 * torch.randn(B, 160 * T, generator=g)).cuda()
+        npos = B * 160 * T
+        legs = [("forward()", 1, lambda: m.forward(x, per, feat))]
+        for btn in (32, 16):
+            legs.append((f"loss_backward btn={btn}", 3, lambda btn=btn: (m.set_backward_tile(btn), m.loss_backward(x, per, feat, y))))
+        if B == 16:
+            legs.append(("torch autograd f32", 3, torch_step(sd, x, m.upsample(feat, per), y)))
+        fwd = None
+        for name, k, fn in legs:
+            lo, med, hi = timed(fn)
+            fwd = fwd or lo
+            fl = 2 * k * mac * npos / (lo * 1e-3)
+            lines.append(f"{name:>22s} {B:4d} {npos:9d} {lo:9.2f} / {med:.2f} / {hi:.2f} {fl / 1e12:10.2f} {100 * fl / PEAK:10.2f} % {lo / fwd:12.2f} x")
+            print(lines[-1], flush=True)
+        m.set_backward_tile(0)
+        lines.append(f"  workspace {m.backward_workspace_bytes(B, T) / 1e9:.2f} GB")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/wavenet_decode.txt, with --forward profiles/wavenet_forward.txt")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--frames", type=int, default=10)
     ap.add_argument("--forward", action="store_true", help="time the teacher-forced pass instead of the sample loop")
+    ap.add_argument("--backward", action="store_true", help="time loss_backward beside forward() and torch autograd")
     a = ap.parse_args()
-    a.out = a.out or ("profiles/wavenet_forward.txt" if a.forward else "profiles/wavenet_decode.txt")
+    a.out = a.out or ("profiles/wavenet_backward.txt" if a.backward else "profiles/wavenet_forward.txt" if a.forward
+                      else "profiles/wavenet_decode.txt")
     _lib.require_gpu()
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     T, N, L = a.frames, a.frames * 160, NB * NL
     mac = R * 32 + L * (2 * G * (2 * R + CO) + (R + S) * G) - R * G + S * S + 2 * S
-    if a.forward:
-        lines = forward_leg(a, mac)
+    if a.forward or a.backward:
+        lines = backward_leg(a, mac) if a.backward else forward_leg(a, mac)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
